@@ -13,11 +13,20 @@ region is exactly K steps bracketed by barrier + synchronize; warm-up is W steps
 --min-warmup-ms of back-to-back launches (the clocks settle). roofline.achieved is the timed
 region's bytes over the timed region's GPU time (HIP events on the launch stream).
 
-After timing, the timed configuration itself is checked: one more replay of launch 0, then batch
-0's records are SHA-256 compared with tests/golden/digests.json (the compiled reference's output
-for the same seed) and the launch's last batch is compared record for record with the C oracle.
+A plain run does only that: set up, warm up, time the K steps, write the outputs when
+--dump-outputs is given, print the line. --dump-outputs DIR writes what the last timed step's launch
+returned to its caller (the line count of each of its batches, and a fixed seeded sample of their
+records, field by field) as DIR/<name>.npy; the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5]
+Everything else is behind --full. There, after timing, the timed configuration itself is checked:
+one more replay of launch 0, then batch 0's records are SHA-256 compared with
+tests/golden/digests.json (the compiled reference's output for the same seed) and the launch's last
+batch is compared record for record with the C oracle. --full also measures the streaming-read
+ceiling (roofline.read_ceiling), the CPU baseline, the end-to-end (e2e) and route + pack legs and the
+regroup leg; --no-cpu, --no-e2e, --no-verify, --no-pack and --regroup choose among them.
+
+  python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5] [--dump-outputs DIR] [--full]
   --gpus N > 1 without WORLD_SIZE: re-launches itself under torch.distributed.run (N ranks, one per
   GPU; each rank routes its own batches: weak scaling, no collective on the classify path) plus a
   classify + regroup leg over RCCL on C5-shaped batches.
@@ -68,6 +77,13 @@ def parse(argv=None):
     ap.add_argument("--min-warmup-ms", type=float, default=60.0,
                     help="keep warming up until this much time has passed (clocks settle)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the checks and the other measurements: verification "
+                         "against the reference digest and the oracle, the read ceiling, the CPU baseline, the "
+                         "e2e, route + pack and regroup legs (each as its own option says)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (line counts, a seeded sample of the records) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--batches", type=int, default=64, help="distinct batches in the rotating set")
     ap.add_argument("--per-launch", type=int, default=32, help="batches per route_kernel launch (one step)")
     ap.add_argument("--dead", type=float, default=0.0,
@@ -106,7 +122,10 @@ def parse(argv=None):
     # the PMC counter bytes of the dominant kernel (tools/pmc_summary.py): at the top of the tree so
     # that it travels to the GPU box with the library it was measured on (profiles/ does not)
     ap.add_argument("--traffic-json", default=os.path.join(REPO, "bench_traffic.json"))
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.regroup == "on" and not args.full:
+        ap.error("--regroup on needs --full (a plain run times the route launches only)")
+    return args
 
 
 def free_port() -> int:
@@ -260,10 +279,15 @@ def main(argv=None):
 
     counts = d_cnt.cpu().numpy()
     assert all(int(counts[b]) == lines[b] for b in range(B)), "line counts differ from the generator"
-    verify = None if args.no_verify else verify_timed_launch(pkg, graphs[0], stream, d_out, host, M, max_lines,
-                                                             shards, alive, rank, digests, dkey, alive_tag)
+    if args.dump_outputs and rank == 0:   # before anything else launches into d_out
+        last = (K - 1) % ng
+        dump_outputs(pkg, args.dump_outputs, d_out, counts[last * M: last * M + M], lines[last * M: last * M + M])
+    verify = None
+    if args.full and not args.no_verify:
+        verify = verify_timed_launch(pkg, graphs[0], stream, d_out, host, M, max_lines, shards, alive, rank,
+                                     digests, dkey, alive_tag)
 
-    ceiling = read_ceiling(d_in, stream)
+    ceiling = read_ceiling(d_in, stream) if args.full else {"note": "measured with --full"}
     wall = t1 - t0
     steps_lines = sum(group_lines[i % ng] for i in range(K))
     steps_bytes = sum(group_bytes[i % ng] for i in range(K))
@@ -346,11 +370,11 @@ def main(argv=None):
             "cpu_baseline": None,
         }
 
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             result["cpu_baseline"] = cpu_baseline(host, shards, alive, args.cpu_seconds)
-        if not args.no_e2e:
+        if args.full and not args.no_e2e:
             result["e2e"] = e2e(pkg, router, stream, host, sizes, lines, batch_bytes, dev, M)
-        if not args.no_pack:
+        if args.full and not args.no_pack:
             result["route_pack"] = pack_leg(pkg, router, stream, d_in, sizes, lines, batch_bytes, shards, M, dev,
                                             dead=sum(alive) < shards, alive=alive, threads=args.pack_threads,
                                             host=None if args.no_verify else host, knobs=args.knob,
@@ -370,7 +394,7 @@ def main(argv=None):
         return False
 
     dog = None
-    if args.regroup == "on" or (args.regroup == "auto" and world > 1):
+    if args.full and (args.regroup == "on" or (args.regroup == "auto" and world > 1)):
         # a collective that never completes (a peer lost, a transport stuck) must not take the main
         # line with it: past the deadline every rank prints what it has and leaves
         def give_up():
@@ -406,6 +430,31 @@ def apply_knobs(pkg, router, knobs):
     for kv in knobs:
         name, _, val = kv.partition("=")
         router.set_knob(getattr(pkg, "SR_KNOB_" + name.upper()), int(val, 0))
+
+
+DUMP_SAMPLE = 1 << 20   # records written by --dump-outputs: 16 B each over the three field files
+DUMP_SEED = 0x5EEDD0
+
+
+def dump_outputs(pkg, dirname, d_out, counts, lines):
+    """--dump-outputs: what the last timed step's launch returned, as float arrays.
+
+    counts.npy: the line count the launch wrote for each of its batches (float64). record_offset.npy
+    (float64), record_length.npy and record_route.npy (float32, 16-bit fields): the records of all its
+    batches taken as one sequence, batch after batch, each batch's first lines[m] records (the
+    generator's count, so the positions depend on the inputs alone); at most DUMP_SAMPLE of them, at
+    positions drawn once from DUMP_SEED and sorted."""
+    import numpy as np
+
+    recs = d_out.cpu().numpy()
+    flat = np.concatenate([recs[m, : n * 8] for m, n in enumerate(lines)]).view(pkg.RECORD_DTYPE)
+    if flat.size > DUMP_SAMPLE:
+        flat = flat[np.sort(np.random.default_rng(DUMP_SEED).choice(flat.size, DUMP_SAMPLE, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "counts.npy"), np.asarray(counts, dtype=np.float64))
+    np.save(os.path.join(dirname, "record_offset.npy"), flat["offset"].astype(np.float64))
+    np.save(os.path.join(dirname, "record_length.npy"), flat["length"].astype(np.float32))
+    np.save(os.path.join(dirname, "record_route.npy"), flat["route"].astype(np.float32))
 
 
 def read_ceiling(d_in, stream, reps=20):

@@ -33,6 +33,17 @@ def test_one_gpu_runs_in_process():
     assert ranks == [{"RANK": None, "LOCAL_RANK": None, "WORLD_SIZE": None, "MASTER_ADDR": None}]
 
 
+def test_other_legs_are_behind_full():
+    import bench
+
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert plain.full is False and plain.dump_outputs is None and plain.steps == 7
+    full = bench.parse(["--full", "--regroup", "on", "--dump-outputs", "d"])
+    assert full.full is True and full.regroup == "on" and full.dump_outputs == "d"
+    p = _run(["--regroup", "on", "--dry-ranks"])   # asked for a leg a plain run does not have
+    assert p.returncode == 2 and "--full" in p.stderr
+
+
 def test_gpus_must_match_world_size():
     p = _run(["--gpus", "4", "--dry-ranks"], {"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert p.returncode != 0 and "WORLD_SIZE=2" in (p.stderr + p.stdout)

@@ -9,7 +9,7 @@ for r in $(seq 1 "$rounds"); do
   for a in "$@"; do
     for d in ${libs//,/ }; do
       lib=""; [ "$d" != "-" ] && lib="$d/libsr_route.so"
-      line=$(SR_ROUTE_LIB=$lib timeout -k 10 200 python bench.py --no-cpu --no-e2e $a 2>"$out.err") || { tail -20 "$out.err"; exit 1; }
+      line=$(SR_ROUTE_LIB=$lib timeout -k 10 200 python bench.py --full --no-cpu --no-e2e $a 2>"$out.err") || { tail -20 "$out.err"; exit 1; }
       python -c "import json,sys; d=json.loads(sys.argv[1]); d['ab_lib']=sys.argv[2]; d['ab_args']=sys.argv[3]; d['ab_round']=int(sys.argv[4]); print(json.dumps(d))" "$line" "$d" "$a" "$r" >> "$out"
       echo "round $r lib $d args $a done"
     done

@@ -6,7 +6,7 @@ rounds=$1; cfg=$2; shift 2
 mkdir -p gpurun_out
 for r in $(seq 1 $rounds); do
   for d in "$@"; do
-    out=$(SR_ROUTE_LIB=$d/libsr_route.so timeout -k 10 120 python bench.py --config $cfg --no-cpu --no-e2e --no-verify --regroup off --steps 5 --warmup 2 2>/dev/null) || exit 1
+    out=$(SR_ROUTE_LIB=$d/libsr_route.so timeout -k 10 120 python bench.py --full --config $cfg --no-cpu --no-e2e --no-verify --regroup off --steps 5 --warmup 2 2>/dev/null) || exit 1
     python -c "import json,sys; d=json.loads(sys.argv[1]); print(json.dumps({'lib': sys.argv[2], 'cfg': sys.argv[3], 'packing_ms': d['route_pack']['packing_ms']}))" "$out" "$d" "$cfg" >> gpurun_out/ab_mtu.jsonl
   done
 done

@@ -7,6 +7,6 @@ tar --exclude=./gpurun_out --exclude=./.git -cf - . | tar -C /tmp/abold -xf -
 cp tools/dbg/old/regroup.py /tmp/abold/statsd-router_amd/regroup.py
 cp tools/dbg/old/bench.py /tmp/abold/bench.py
 for rep in 1 2; do
-  r=$(timeout -k 10 120 python bench.py --regroup on --regroup-steps 64 --no-cpu --no-e2e --steps 256 --warmup 64 2>/dev/null); echo "new $r" >> $out
+  r=$(timeout -k 10 120 python bench.py --full --regroup on --regroup-steps 64 --no-cpu --no-e2e --steps 256 --warmup 64 2>/dev/null); echo "new $r" >> $out
   r=$(cd /tmp/abold && timeout -k 10 120 python bench.py --regroup on --regroup-steps 64 --no-cpu --no-e2e --steps 256 --warmup 64 2>/dev/null); echo "old $r" >> $out
 done

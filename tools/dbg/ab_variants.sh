@@ -8,7 +8,7 @@ for rep in 1 2; do
   for c in ${CONFIGS:-c2 c4}; do
     for v in ${VARIANTS:-default agent_granules}; do
       vv=$v; [ "$v" = default ] && vv=""
-      r=$(SR_VARIANT=$vv timeout -k 10 120 python bench.py --config $c --no-cpu --no-e2e --steps 1024 2>/dev/null)
+      r=$(SR_VARIANT=$vv timeout -k 10 120 python bench.py --full --config $c --no-cpu --no-e2e --steps 1024 2>/dev/null)
       echo "$c $v $r" >> $out
     done
   done
