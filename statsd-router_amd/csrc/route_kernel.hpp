@@ -14,9 +14,11 @@
 // One kernel, one pass over the bytes:
 //   * A launch routes up to 32 batches. Blocks 0 .. nb-1 are per-batch SCANNERS; every other block
 //     routes one 16 KiB TILE with 256 threads (4 waves), 64 contiguous bytes per thread, up to 7
-//     workgroups per CU (71-72 VGPRs, ~22.5 KiB of LDS). With 8+ batches each batch's tiles and its
+//     workgroups per CU (65-72 VGPRs, ~22.5 KiB of LDS); the every-shard-alive uniform variant fits 8
+//     (kOcc8: 63 VGPRs, 78 SGPRs, 20 KiB of LDS). With 8+ batches each batch's tiles and its
 //     scanner share one XCD class (blocks b and b + 8 land on the same XCD).
-//   * Tile entry: four buffer_load_dwordx4 per thread (+ 2 KiB of halo before the tile) into a padded
+//   * Tile entry: four buffer_load_dwordx4 per thread (+ 2 KiB of halo before the tile, 1.5 KiB in
+//     the kOcc8 variant) into a padded
 //     LDS image (17-dword rows: conflict-free per-thread rows); '\n' and ':' bit masks of the
 //     thread's 64 bytes from the load registers (8 VALU per dword for both patterns); the tile's '\n'
 //     count published at once in a status granule for the scanner.
@@ -793,8 +795,18 @@ __device__ __forceinline__ void mark_tile_end(const RouteParams &p, const uint32
 // ---------------------------------------------------------------------------------------
 // The route kernel
 // ---------------------------------------------------------------------------------------
-template <int BLOCK>
+// The every-shard-alive uniform variant (every launch without a dead shard and without mixed line
+// lengths: C2, C3, C4) is budgeted for eight workgroups per CU, one more than the others: at most
+// 20,480 bytes of LDS (SmemT's SLIM shape), 64 VGPRs and 80 SGPRs. The SGPR bound is the hardware's:
+// a 256-thread workgroup is admitted min(8, floor(800 / (ceil(sgpr / 16) * 16 + 16))) times per CU,
+// which is 7 from 81 SGPRs on, whatever the occupancy query and the compiler's remark say.
+// (ABL_STAMPS, the diagnostic build of tools/stamps_route.hip, keeps the shape of what it stamps.)
+template <int BLOCK, unsigned ABL>
+constexpr bool kOcc8 = BLOCK == 256 && (ABL & ~ABL_STAMPS) == (KV_UNIFORM | KV_ALIVE);
+
+template <int BLOCK, bool SLIM = false>
 struct SmemT {
+    typedef int32_t pos_t;
     static constexpr int kWaves = BLOCK / 64;
     static constexpr int kTileB = BLOCK * kLaneBytes;
     static constexpr int kHalo = 2048;                // bytes before the tile kept in LDS
@@ -824,7 +836,56 @@ struct SmemT {
     uint32_t hist[kHistKeys];        // RouteParams::hist: the tile's records per key
     uint32_t epoch, base;
     uint32_t scan_head, scan_pub, scan_total;   // scanner: bases computed / published, line total
+    // word w of RouteParams::kpow, stored at tile entry; K^r for the r < 4 bytes of a name's last dword
+    __device__ __forceinline__ void put_pow(int w, uint32_t v) { ((uint32_t *)&kp_lo[0])[w] = v; }   // kp_lo | kp_hi | kp_inv are contiguous
+    __device__ __forceinline__ uint64_t pow_rem(int r) const { return kp_lo[r]; }
 };
+
+// The shape for eight workgroups per CU (kOcc8): 20,360 bytes.
+//  * halo of 1536 bytes: a valid line is at most 1449 bytes, so one that straddles into the tile
+//    starts at most 1448 bytes before it; a line that starts further back is invalid whatever it
+//    holds, and its start is found in global memory as before;
+//  * line ends and first colons as 16-bit tile positions (below 16384; 0xFFFF = no colon, above
+//    any line end just as kNone is);
+//  * no segment-layout arrays (KV_SEGMENTS only);
+//  * the power tables K^i and K^(64 i) in the pad dwords of image rows 0 .. 2 (kPowLo + kPowHi) - 1
+//    (entry i: low word in row 2 i, high word in row 2 i + 1), which only the probes of the
+//    dead-shard variants use otherwise; they are read for names of more than 64 bytes only. K^r
+//    (r < 4), read once per line, stays an array of its own.
+template <int BLOCK>
+struct SmemT<BLOCK, true> {
+    typedef uint16_t pos_t;
+    static constexpr int kWaves = BLOCK / 64;
+    static constexpr int kTileB = BLOCK * kLaneBytes;
+    static constexpr int kHalo = 1536;
+    static constexpr int kWin = BLOCK;
+    static constexpr int kRows = (kHalo + kTileB) / 64;
+    static constexpr int kWords = kRows * 17 + 20;
+    static constexpr int kPowWords = (kPowLo + kPowHi) * 2;
+    static_assert(kHalo >= (int)SR_MAX_LINE_LENGTH - 1 && kHalo % 64 == 0 && kHalo >= 512, "halo holds every valid straddler");
+    static_assert(kTileB < 0xFFFF, "16-bit tile positions");
+    static_assert(kPowWords <= kRows, "power tables in the pad dwords");
+    uint32_t img[kWords];
+    uint64_t kp_rem[4];
+    uint16_t lend[kWin + 1];
+    uint16_t lcol[kWin + 1];
+    uint32_t wave_cnt[kWaves];
+    uint32_t wave_scan[kWaves][4];
+    int32_t s_pre, c_pre;
+    uint32_t hist[kHistKeys];
+    uint32_t epoch, base;
+    uint32_t scan_head, scan_pub, scan_total;
+    __device__ __forceinline__ void put_pow(int w, uint32_t v) {
+        img[w * 17 + 16] = v;
+        if (w < 8) ((uint32_t *)&kp_rem[0])[w] = v;
+    }
+    __device__ __forceinline__ uint64_t pow_rem(int r) const { return kp_rem[r]; }
+    __device__ __forceinline__ uint64_t pow_lo(int i) const {
+        return ((uint64_t)img[(2 * i + 1) * 17 + 16] << 32) | img[(2 * i) * 17 + 16];
+    }
+    __device__ __forceinline__ uint64_t pow_hi(int i) const { return pow_lo(kPowLo + i); }
+};
+static_assert(sizeof(SmemT<256, true>) <= 20480, "eight workgroups per CU: 160 KiB of LDS");
 
 // K^-z for z = 1, 2, 3 (undoing z bytes of zero padding)
 __device__ __forceinline__ uint64_t kinv_small(int z) {
@@ -836,6 +897,10 @@ __device__ __forceinline__ uint64_t kinv_small(int z) {
 template <class S>
 __device__ __forceinline__ uint64_t kpow_n(const S &sm, int n) {
     return sm.kp_hi[n >> 6] * sm.kp_lo[n & 63];
+}
+template <int BLOCK>
+__device__ __forceinline__ uint64_t kpow_n(const SmemT<BLOCK, true> &sm, int n) {
+    return sm.pow_hi(n >> 6) * sm.pow_lo(n & 63);
 }
 
 // dword index in the padded LDS image of image byte b (b % 4 == 0 for whole dwords)
@@ -897,7 +962,7 @@ __device__ __forceinline__ uint64_t sdbm_img(const S &sm, int a, int n, const ui
     for (; m + 3 < F; m += 4)
         h = sdbm_qword_fast(sdbm_qword_fast(h, p[m + 1], p[m + 2]), p[m + 3], p[m + 4]);
     for (; m < F; ++m) h = sdbm_dword_fast(h, p[m + 1]);
-    if (rem) h = h * sm.kp_lo[rem] + sdbm_dword_fast(0, p[m + (m >= cross ? 1 : 0)] << (8 * (4 - rem)));
+    if (rem) h = h * sm.pow_rem(rem) + sdbm_dword_fast(0, p[m + (m >= cross ? 1 : 0)] << (8 * (4 - rem)));
     return h;
 }
 
@@ -1262,6 +1327,13 @@ __device__ uint32_t wait_base(const uint64_t *slot, uint32_t epoch, __amdgpu_buf
 __device__ __forceinline__ void arrive_count(const RouteParams &p, uint32_t blk) {
     __hip_atomic_fetch_add(&p.ctl->done[blk & 7u][0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// An arrival ahead of the block's end: the epoch's value must be in hand before the block counts as
+// arrived (the last block advances the epoch once all have). The atomic's operand is made to depend
+// on the loaded epoch, so the wait for that load precedes the atomic whatever the schedule.
+__device__ __forceinline__ void arrive_count_after(const RouteParams &p, uint32_t blk, uint32_t epoch) {
+    asm volatile("" : : "v"(epoch) : "memory");
+    __hip_atomic_fetch_add(&p.ctl->done[blk & 7u][0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 __device__ void arrive_last(const RouteParams &p, uint32_t blk, uint32_t epoch) {
     if (blk != p.total_blocks - 1) return;
     for (uint32_t spin = 0; spin < (1u << 26); ++spin) {
@@ -1293,15 +1365,18 @@ __device__ void arrive(const RouteParams &p, uint32_t blk, uint32_t epoch) {
 // A tile's arrival right after it has read the epoch (the invariant above holds all the same), not
 // at its end: the atomic's round trip then runs under the tile's loads instead of after its last
 // store. Segment-layout launches keep the arrival at the end: their tiles add the layout statistics
-// in their last window, which the last block reads once everyone has arrived.
+// in their last window, which the last block reads once everyone has arrived. So does the full-probe
+// variant (no KV_ bit: two or more dead shards and no scratch to defer to), which sits at its
+// register limit: the early arrival's wait for the epoch costs it a VGPR spill to scratch.
 template <unsigned ABL>
-constexpr bool kEarlyArrive = (ABL & KV_SEGMENTS) == 0;
+constexpr bool kEarlyArrive = (ABL & KV_SEGMENTS) == 0 && (ABL & (KV_ALIVE | KV_PICKS | KV_DEFER1 | KV_DEAD1)) != 0;
 
 template <int BLOCK, unsigned ABL>
 struct KernelTraits {
     // waves per SIMD to reserve registers for: 1024-thread tiles run one workgroup per CU,
     // smaller tiles several (LDS: 86 KB / 45 KB / 24 KB per workgroup)
-    static constexpr int kMinWavesPerSimd = BLOCK >= 1024 ? 4 : (BLOCK >= 512 ? 6 : 7);
+    // (kOcc8: eight workgroups of four waves per CU, 64 VGPRs)
+    static constexpr int kMinWavesPerSimd = BLOCK >= 1024 ? 4 : (BLOCK >= 512 ? 6 : (kOcc8<BLOCK, ABL> ? 8 : 7));
     static constexpr int kMaxWavesPerSimd = 8;
     static constexpr int kMaxVgpr = 512 / kMinWavesPerSimd / 8 * 8;   // 72 for 7 waves per SIMD
 };
@@ -1346,7 +1421,7 @@ __device__ __forceinline__ uint32_t launch_header_batch(uint4 &hdr) {
 
 // One tile's input as loaded into registers: thread tid holds the tile's bytes [64 tid, 64 tid + 64)
 // in v[0..3] (its own chunk: every wave-instruction still reads one contiguous 4 KiB span), and
-// threads below kHalo/16 hold 16 bytes of the 2 KiB before the tile.
+// threads below kHalo/16 hold 16 bytes of the halo before the tile.
 struct TileIn {
     uint32_t bi, t;
     uint64_t sx;   // the batch scanner's kFlagXcc granule
@@ -1357,7 +1432,7 @@ struct TileIn {
 template <int BLOCK, unsigned ABL>
 __device__ __forceinline__ void tile_issue(const RouteParams &p, uint32_t bi, uint32_t t, TileIn &in, int tid) {
     constexpr int kTileB = BLOCK * kLaneBytes;
-    constexpr int kHalo = SmemT<BLOCK>::kHalo;
+    constexpr int kHalo = SmemT<BLOCK, kOcc8<BLOCK, ABL>>::kHalo;
     const BatchDesc &bd = p.b[bi];
     const uint32_t T0 = t * (uint32_t)kTileB;
     const __amdgpu_buffer_rsrc_t rsrc =
@@ -1396,10 +1471,9 @@ __device__ __forceinline__ void prefetch_sink(uint32_t v) { asm volatile("" ::"v
 // the registers of `in` into the LDS image (thread tid's chunk = image row tid), the '\n' / ':'
 // masks of the thread's 64 bytes (bit i = byte 64 tid + i) into nlm / clm, and the tile's '\n'
 // count published for the scanner.
-template <int BLOCK, unsigned ABL>
-__device__ __forceinline__ void tile_load(const RouteParams &p, SmemT<BLOCK> &sm, const TileIn &in, uint32_t epoch,
+template <int BLOCK, unsigned ABL, class S>
+__device__ __forceinline__ void tile_load(const RouteParams &p, S &sm, const TileIn &in, uint32_t epoch,
                                           uint32_t g, uint64_t &nlm, uint64_t &clm, uint32_t &c_in) {
-    using S = SmemT<BLOCK>;
     constexpr int kWaves = S::kWaves;
     constexpr int kHalo = S::kHalo;
     const int tid = threadIdx.x;
@@ -1450,11 +1524,11 @@ __device__ __forceinline__ void tile_load(const RouteParams &p, SmemT<BLOCK> &sm
 
 // Second half: lines, hashes, shards and records of the tile whose bytes tile_load left in the
 // LDS image and whose chunk masks are in nlm / clm.
-template <int BLOCK, unsigned ABL>
-__device__ __forceinline__ void tile_lines(const RouteParams &p, SmemT<BLOCK> &sm, const TileIn &in, uint32_t epoch,
+template <int BLOCK, unsigned ABL, class S>
+__device__ __forceinline__ void tile_lines(const RouteParams &p, S &sm, const TileIn &in, uint32_t epoch,
                                            uint32_t g, uint64_t nlm, uint64_t clm, uint32_t c_in) {
     stamp<ABL>(p, threadIdx.x, g, 1);
-    using S = SmemT<BLOCK>;
+    typedef typename S::pos_t pos_t;
     constexpr int kWaves = S::kWaves;
     constexpr int kTileB = S::kTileB;
     constexpr int kHalo = S::kHalo;
@@ -1548,9 +1622,12 @@ __device__ __forceinline__ void tile_lines(const RouteParams &p, SmemT<BLOCK> &s
                 c_pre = (int)__builtin_amdgcn_readlane(fb + __builtin_ctz(cm8 | 0x100u), Lc) - kHalo;
             }
         } else if (t > 0 && !(ABL & ABL_NO_PROLOGUE)) {
-            // the halo: lane l looks at LDS bytes [32l, 32l + 32) = positions T0 - 2048 + 32l ...
+            // the halo: lane l looks at LDS bytes [32l, 32l + 32) = positions T0 - kHalo + 32l ...
+            // (lanes past the halo's kHalo / 32 pieces hold the tile's own bytes: not looked at)
+            static_assert(kHalo <= 2048 && kHalo % 32 == 0, "32 halo bytes per lane");
+            const bool in_halo = 32 * lane < kHalo;
             const uint4 a0 = img_get16(sm, 32 * lane), a1 = img_get16(sm, 32 * lane + 16);
-            const uint32_t nl32 = eq_mask16(a0, 0x0A0A0A0Au) | (eq_mask16(a1, 0x0A0A0A0Au) << 16);
+            const uint32_t nl32 = in_halo ? eq_mask16(a0, 0x0A0A0A0Au) | (eq_mask16(a1, 0x0A0A0A0Au) << 16) : 0u;
             const uint64_t m = __ballot(nl32 != 0);
             if (m) {
                 const int L = 63 - __builtin_clzll(m);
@@ -1577,7 +1654,7 @@ __device__ __forceinline__ void tile_lines(const RouteParams &p, SmemT<BLOCK> &s
             const int s_rel = (int)(s_abs - T0);
             if (s_rel < 0 && -s_rel <= (int)SR_MAX_LINE_LENGTH - 1) {   // could be valid: first ':' before T0
                 const int b0 = kHalo + s_rel - 32 * lane;   // first LDS byte of the line within my 32
-                const uint32_t keep = b0 <= 0 ? 0xFFFFFFFFu : (b0 >= 32 ? 0u : ~((1u << b0) - 1u));
+                const uint32_t keep = !in_halo ? 0u : b0 <= 0 ? 0xFFFFFFFFu : (b0 >= 32 ? 0u : ~((1u << b0) - 1u));
                 const uint32_t cm = (eq_mask16(a0, 0x3A3A3A3Au) | (eq_mask16(a1, 0x3A3A3A3Au) << 16)) & keep;
                 const uint64_t cb = __ballot(cm != 0);
                 if (cb) {
@@ -1614,8 +1691,8 @@ __device__ __forceinline__ void tile_lines(const RouteParams &p, SmemT<BLOCK> &s
                     c = cm ? o + __builtin_ctzll(cm) : kNone;
                 }
                 if (idx >= wbase && idx < wbase + kWin) {
-                    sm.lend[idx - wbase + 1] = o + b;
-                    sm.lcol[idx - wbase + 1] = c;
+                    sm.lend[idx - wbase + 1] = (pos_t)(o + b);
+                    sm.lcol[idx - wbase + 1] = (pos_t)c;   // 16-bit positions: kNone is stored as 0xFFFF
                 }
                 ++idx;
                 prevb = b;
@@ -1634,8 +1711,8 @@ __device__ __forceinline__ void tile_lines(const RouteParams &p, SmemT<BLOCK> &s
             if (nlm) {
                 const int b = __builtin_ctzll(nlm);
                 const uint64_t cm = clm & (b == 0 ? 0ull : (~0ull >> (64 - b)));
-                sm.lend[lane_first + 1] = o + b;
-                sm.lcol[lane_first + 1] = open_fc != kNone ? open_fc : (cm ? o + __builtin_ctzll(cm) : kNone);
+                sm.lend[lane_first + 1] = (pos_t)(o + b);
+                sm.lcol[lane_first + 1] = (pos_t)(open_fc != kNone ? open_fc : (cm ? o + __builtin_ctzll(cm) : kNone));
             }
         } else {
             stage(0, nlm, clm, lane_first, open_fc);
@@ -1705,6 +1782,7 @@ __device__ __forceinline__ void tile_lines(const RouteParams &p, SmemT<BLOCK> &s
             auto line_at = [&](int j, int e, int c, int s, bool act, int gi, int Gl, int Gw) {
                 const int len = e - s + 1;
                 const bool len_ok = len >= (int)SR_MIN_LINE_LENGTH && len <= (int)SR_MAX_LINE_LENGTH;   // :180
+                // (a staged 16-bit position reads 0xFFFF for "no colon": above every line end, as kNone is)
                 const bool fmt_ok = c != kNone && c < e;                                                // :140
                 uint64_t h = 0;
                 if (act && len_ok && fmt_ok && !(ABL & ABL_NO_HASH)) {
@@ -1744,7 +1822,7 @@ __device__ __forceinline__ void tile_lines(const RouteParams &p, SmemT<BLOCK> &s
             // (the segment variant decides in a tile's last window, after which the lane masks and
             // line states of later windows are dead)
             const bool last_win = wbase + kWin >= (int)tile_count;
-            if ((ABL & KV_SEGMENTS) && last_win) {
+            if constexpr ((ABL & KV_SEGMENTS) != 0) if (last_win) {
                 // per line: 64-byte name segments, one lane each (an empty name still takes one)
                 uint32_t want = 0, nsg = 0;
                 if (tid < nwin) {
@@ -1810,7 +1888,7 @@ __device__ __forceinline__ void tile_lines(const RouteParams &p, SmemT<BLOCK> &s
                     const int jj = (int)(x >> __builtin_ctz((unsigned)G));
                     line(jj, jj < nwin, (int)(x & (uint32_t)(G - 1)), G, G);
                 }
-            } else {
+            } else if constexpr ((ABL & KV_SEGMENTS) != 0) {
                 for (int r0 = 0; r0 < (int)TL; r0 += BLOCK) {
                     const uint32_t x = (uint32_t)(r0 + tid);
                     const uint32_t k = x >> 6;   // the lane word: wave-uniform
@@ -1851,11 +1929,11 @@ __device__ __forceinline__ void tile_lines(const RouteParams &p, SmemT<BLOCK> &s
                         }
                         // a line's sum from the inclusive wave scan: S(x) - S(head - 1), or S(x) plus
                         // the line's part in the previous word (a line spans at most 23 lanes)
-                        const uint64_t S = wave_scan64(hs, 0ull, [](uint64_t l, uint64_t r) { return l + r; });
+                        const uint64_t Sx = wave_scan64(hs, 0ull, [](uint64_t l, uint64_t r) { return l + r; });
                         const int src = hb > 0 ? hb - 1 : 0;
-                        const uint64_t Sb = ((uint64_t)(uint32_t)__shfl((int)(S >> 32), src, 64) << 32) |
-                                            (uint32_t)__shfl((int)(uint32_t)S, src, 64);
-                        part = hb > 0 ? S - Sb : S;
+                        const uint64_t Sb = ((uint64_t)(uint32_t)__shfl((int)(Sx >> 32), src, 64) << 32) |
+                                            (uint32_t)__shfl((int)(uint32_t)Sx, src, 64);
+                        part = hb > 0 ? Sx - Sb : Sx;
                         if (lane == 63 && act && sg < glast) sm.seg_carry[k] = part;   // continues in word k + 1
                     }
                     wg_barrier();
@@ -1896,7 +1974,7 @@ __device__ __forceinline__ void tile_lines(const RouteParams &p, SmemT<BLOCK> &s
 template <int BLOCK, unsigned ABL>
 __global__ __launch_bounds__(BLOCK, (KernelTraits<BLOCK, ABL>::kMinWavesPerSimd))
 __attribute__((amdgpu_waves_per_eu((KernelTraits<BLOCK, ABL>::kMinWavesPerSimd), (KernelTraits<BLOCK, ABL>::kMaxWavesPerSimd)))) void route_kernel(RouteParams p) {
-    using S = SmemT<BLOCK>;
+    using S = SmemT<BLOCK, kOcc8<BLOCK, ABL>>;
     __shared__ S sm;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -1959,8 +2037,8 @@ __attribute__((amdgpu_waves_per_eu((KernelTraits<BLOCK, ABL>::kMinWavesPerSimd),
     in.sx = (ABL & ABL_AGENT_GRANULES) ? 0ull
                                        : __hip_atomic_load(&p.ctl->scan_xcc[bi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t ep0 = __hip_atomic_load(&p.ctl->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (kEarlyArrive<ABL> && tid == 0) arrive_count(p, blockIdx.x);
-    if (tid < S::kPowWords) ((uint32_t *)&sm.kp_lo[0])[tid] = kp;   // kp_lo | kp_hi | kp_inv are contiguous
+    if (kEarlyArrive<ABL> && tid == 0) arrive_count_after(p, blockIdx.x, ep0);
+    if (tid < S::kPowWords) sm.put_pow(tid, kp);
     if (!(ABL & (KV_ALIVE | KV_DEFER1 | KV_DEAD1)) && p.dead && p.dead < p.nds && tid < 4 * (int)kMagicLds) {   // the probe's first reciprocals (probe_shard)
         const uint32_t e = (uint32_t)tid >> 2;   // divisor nds - e >= 1: entries e < nds only
         if (e < p.nds) sm.img[(uint32_t)tid * 17 + 16] = ((const uint32_t *)&p.magic[p.nds - e])[tid & 3];

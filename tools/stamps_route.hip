@@ -137,8 +137,41 @@ void run_many(DeviceState &ds, std::vector<uint8_t *> &batches, std::vector<size
             starts[(x.first - a) / 100] += 1;
             for (uint64_t t = x.first; t < x.second; t += 10) occ[(t - a) / 100] += 0.1;
         }
-        printf("{\"residency\": {\"span_us\": %.2f, \"mean_resident_tiles\": %.1f, \"per_us\": [", (z - a) * 0.01,
-               busy / (double)(z - a));
+        // workgroups alive at once on one CU, from the placement stamp (HW_ID bits 8..15: CU, SH, SE; XCC_ID)
+        // and the entry / exit stamps. A workgroup holds its slot from before its entry stamp until after
+        // its exit stamp, so the count is a lower bound; scanner blocks are not stamped and not counted.
+        // This is the residency of this ABL_STAMPS build (its VGPRs, LDS and scratch below; its SGPRs are in
+        // the compiler's -Rpass-analysis=kernel-resource-usage remark only), not the shipped kernel's.
+        int max_per_cu = 0, cus = 0, cus_at_max = 0;
+        {
+            std::vector<std::vector<std::pair<uint64_t, int>>> ev(8 * 256);
+            for (uint32_t b = 0; b < total; ++b) {
+                const uint64_t *d = h.data() + (size_t)b * 16;
+                if (!d[8] || !d[9]) continue;
+                const size_t cu = (size_t)(d[11] & 7u) * 256 + ((d[10] >> 8) & 0xFFu);
+                ev[cu].push_back({d[8], +1});
+                ev[cu].push_back({d[9], -1});
+            }
+            for (auto &e : ev) {
+                if (e.empty()) continue;
+                ++cus;
+                std::sort(e.begin(), e.end());   // at equal stamps the exit (-1) sorts first
+                int cur = 0, mx = 0;
+                for (auto &x : e) mx = std::max(mx, cur += x.second);
+                if (mx > max_per_cu) max_per_cu = mx, cus_at_max = 0;
+                if (mx == max_per_cu) ++cus_at_max;
+            }
+        }
+        hipFuncAttributes fa{};
+        const void *fn = chunk_layout ? (const void *)route_chunk_kernel<ABL_STAMPS | KV_CHUNKS | KV_ALIVE>
+                         : seg_layout ? (const void *)route_kernel<BLOCK, ABL_STAMPS | KV_SEGMENTS | KV_ALIVE>
+                                      : (const void *)route_kernel<BLOCK, ABL_STAMPS | KV_ALIVE>;
+        CK(hipFuncGetAttributes(&fa, fn));
+        printf("{\"residency\": {\"span_us\": %.2f, \"mean_resident_tiles\": %.1f, \"max_resident_per_cu\": %d, "
+               "\"cus\": %d, \"cus_at_max\": %d, \"stamps_build\": {\"vgprs\": %d, \"lds_bytes\": %zu, "
+               "\"scratch_bytes\": %zu}, \"per_us\": [",
+               (z - a) * 0.01, busy / (double)(z - a), max_per_cu, cus, cus_at_max, fa.numRegs, fa.sharedSizeBytes,
+               fa.localSizeBytes);
         for (int i = 0; i < nb; ++i) printf("%s[%.0f, %.0f]", i ? ", " : "", occ[i], starts[i]);
         printf("]}}\n");
     }
