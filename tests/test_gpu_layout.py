@@ -76,6 +76,7 @@ def test_auto_follows_the_traffic(pkg, oracle):
     uniform = pkg.gen_stream(4 << 20, [1024], seed=0x5EED0004).data
     r = pkg.Router(64, 4 << 20)
     try:
+        r.set_layout(pkg.SR_LAYOUT_AUTO)   # the premise here, also in a run whose contexts start in another (SR_TEST_LAYOUT)
         seen = []
         for data in [mixed, mixed, mixed, uniform, uniform, uniform]:
             _assert_same(r.route(data, want_hashes=True), oracle.route(data, 64), "auto")
