@@ -56,6 +56,7 @@ struct sr_core {
     uint32_t *dg_ends[2];                    /* TRACE: datagram ends of the batch in each slot    */
     size_t dg_n[2], dg_cap[2];
     uint64_t *ping_hash;                     /* TRACE: the ping names' hashes                      */
+    int payloads;                            /* sr_core_set_payloads: packets from the slot's arena */
     int host_fills;                          /* the host changed pending buffers since the last  */
                                              /* submission: upload them with the next one         */
     uint16_t *fill16;
@@ -294,10 +295,36 @@ static void complete(sr_core *c, int slot, const uint8_t *framed, size_t nbytes,
      * records' unrouted tail, in input order */
     if ((!c->trace || trace_batch(c, slot, framed, nbytes) != 0) && c->log_level <= SR_WARN)
         for (size_t i = r->n_valid; i < r->n_records; i++) warn_line(c, framed, &r->sorted[i]);
+    /* sr_core_set_payloads: the packets' lines laid end to end by the GPU, packet q at
+     * arena[offs[q] + carry, offs[q + 1]) (the carry's room is unwritten: the host holds those bytes) */
+    const uint8_t *arena = NULL;
+    const uint32_t *offs = NULL;
+    size_t n_arena = 0;
+    if (c->payloads && (sr_route_pack_payloads(c->ctx, slot, &arena, &offs, &n_arena) != 0 || n_arena != r->n_packets)) {
+        core_log(c, SR_ERROR, "%s: sr_route_pack_payloads() failed", "udp_read_cb");
+        arena = NULL;   /* the line list below serves the batch */
+    }
     for (size_t q = 0; q < r->n_packets; q++) {
         const sr_packet *p = &r->packets[q];
         ds_state *d = &c->ds[p->shard];
         const sr_record *rec = r->sorted + p->first;
+        if (arena) {
+            const uint8_t *lines = arena + offs[q] + p->carry;
+            if (p->open) {   /* the carried bytes are in place already */
+                memcpy(d->pending + p->carry, lines, p->length);
+                d->fill = (uint32_t)p->carry + p->length;
+                continue;
+            }
+            int iv = 0;
+            if (p->carry) c->iov[iv++] = (struct iovec){d->pending, p->carry};
+            if (p->length) c->iov[iv++] = (struct iovec){(void *)lines, p->length};
+            const uint32_t bytes = (uint32_t)p->carry + p->length;
+            d->packets += 1;
+            d->traffic = (int32_t)((uint32_t)d->traffic + bytes);
+            c->emit(c->user, p->shard, c->iov, iv, bytes);
+            d->fill = 0;
+            continue;
+        }
         if (p->open) {
             /* the new active buffer: the carried bytes (already in place) + this batch's lines */
             uint32_t f = p->carry;
@@ -427,6 +454,20 @@ int sr_core_route(sr_core *c, const uint8_t *framed, size_t nbytes) {
 }
 
 sr_ctx *sr_core_context(sr_core *c) { return c ? c->ctx : NULL; }
+
+int sr_core_set_payloads(sr_core *c, int on) {
+    if (!c) return -EINVAL;
+    if (c->in_flight >= 0) return -EBUSY;
+    int rc = sr_set_payloads(c->ctx, on);
+    if (rc) return rc;
+    c->payloads = on ? 1 : 0;
+    /* both slots' arenas allocated now (an empty batch each; the device's pending bytes carry over) */
+    for (int k = 0; on && k < 2; k++) {
+        sr_pack_result r;
+        if ((rc = sr_route_pack_submit(c->ctx, k, NULL, 0, NULL)) || (rc = sr_route_pack_result(c->ctx, k, &r))) return rc;
+    }
+    return 0;
+}
 
 int sr_core_inject_faults(sr_core *c, unsigned fail_submit, unsigned fail_finish) {
     if (!c) return -EINVAL;

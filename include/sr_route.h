@@ -436,6 +436,58 @@ int sr_set_trace(sr_ctx *ctx, int on);
 int sr_route_pack_trace(sr_ctx *ctx, int slot, const sr_record **records, const uint64_t **hashes,
                         size_t *n_records);
 
+/* ---- packet payloads (wire format) ----------------------------------------------------------- */
+/* sr_pack_packets describes the packets; sr_pack_payloads gathers their bytes on the device, as
+ * ds_flush_cb sends them (sr-main.c:21-46): per descriptor its `carry` pending bytes followed by its
+ * `nlines` lines with no padding, the packets back to back in one arena.
+ *   d_offsets[i] = exclusive prefix sum of carry + length over the batch's n = min(d_counts[0],
+ *                  max_packets) descriptors, d_offsets[n] = *d_total = the arena bytes needed;
+ *   d_payload    : bytes [d_offsets[i], d_offsets[i+1]) are packet i (flushed and open packets alike).
+ *                  Nothing at or past min(total, payload_cap) is written: *d_total > payload_cap or
+ *                  d_counts[0] > max_packets tells the caller that the arena is incomplete.
+ *                  SR_PAYLOAD_CAPACITY always suffices;
+ *   d_pend_in    : the pending bytes before the batch, slot s at d_pend_in + s * SR_PENDING_STRIDE. NULL:
+ *                  the first `carry` bytes of a packet are left unwritten (room for a caller that holds
+ *                  the pending bytes on the host and copies them in itself);
+ *   d_pend_out   : NULL, or the pending bytes after the batch in the same layout: slot s receives the
+ *                  bytes of downstream s's open packet, or, when s has no descriptor, the first
+ *                  d_fill_out[s] bytes of d_pend_in's slot (none when s was probed dead). Bytes of a slot
+ *                  at or past d_fill_out[s] are not written. Needs d_pend_in and must not be d_pend_in:
+ *                  a flushed packet reads the slot its downstream's open packet writes, so consecutive
+ *                  batches alternate between two buffers.
+ * Asynchronous on the context's stream, after the packing of the same batches; no scratch, so the calls
+ * can be captured in a graph. count in 1..SR_MAX_BATCHES_PER_LAUNCH. Returns 0, -EINVAL (a null
+ * required pointer, d_pend_out without d_pend_in or equal to it, count out of range), -ENOMEM, -EIO. */
+#define SR_PENDING_STRIDE 1456u   /* one downstream's pending slot: 1450 rounded up to 16 */
+#define SR_PAYLOAD_CAPACITY(nbytes, n_downstreams) \
+    ((uint64_t)(nbytes) + (uint64_t)SR_DOWNSTREAM_BUF_SIZE * (n_downstreams))
+
+typedef struct sr_payload_batch {
+    const uint8_t *d_bytes;  size_t nbytes;        /* the routed batch                               */
+    const sr_record *d_sorted; size_t max_records; /* sr_pack_batch.d_sorted / max_records           */
+    const sr_packet *d_packets; size_t max_packets;
+    const uint64_t *d_counts;                      /* sr_pack_batch.d_counts                         */
+    const uint16_t *d_fill_out;                    /* sr_pack_batch.d_fill_out                       */
+    const uint8_t *d_pend_in;                      /* NULL (room left for the carry) or n * STRIDE   */
+    uint8_t *d_pend_out;                           /* NULL or n * STRIDE; needs d_pend_in; != it     */
+    uint8_t *d_payload;  size_t payload_cap;
+    uint32_t *d_offsets;                           /* max_packets + 1                                */
+    uint64_t *d_total;                             /* bytes needed                                   */
+} sr_payload_batch;
+int sr_pack_payloads_many(sr_ctx *ctx, const sr_payload_batch *batches, size_t count);
+int sr_pack_payloads(sr_ctx *ctx, const sr_payload_batch *batch);   /* count = 1 */
+
+/* The payloads of the host-memory path. With sr_set_payloads(ctx, 1) every later sr_route_pack_submit /
+ * sr_route_pack_batch also gathers the batch's packets (d_pend_in = NULL: the host holds the pending
+ * bytes, so each packet's first `carry` bytes are room) into page-locked memory of the slot;
+ * sr_route_pack_payloads points at the arena and its n_packets + 1 offsets after
+ * sr_route_pack_result(slot), valid until the slot is submitted again (slot 2: the last
+ * sr_route_pack_batch). Off by default: the slot's device-to-host bytes grow from 8 per line to 8 plus the
+ * line. Returns 0, -EINVAL, -EBUSY (the slot is in flight or was submitted with the switch off). */
+int sr_set_payloads(sr_ctx *ctx, int on);
+int sr_route_pack_payloads(sr_ctx *ctx, int slot, const uint8_t **payload, const uint32_t **offsets,
+                           size_t *n_packets);
+
 /* Developer and test knobs of one context (A/B runs and tests only; the library reads no environment
  * variable and no knob changes any record, packet or count, only which kernels produce them):
  *   SR_KNOB_LB_SPIN       polls of a predecessor tile's tail granules before route_chunk_kernel

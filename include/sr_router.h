@@ -102,6 +102,15 @@ int sr_core_submit_datagrams(sr_core *core, int slot, size_t nbytes, const uint3
  * Owned by the core. */
 sr_ctx *sr_core_context(sr_core *core);
 
+/* Packets from the device's arena. With sr_core_set_payloads(core, 1) every later batch also has its
+ * packets' bytes gathered on the GPU (sr_set_payloads, sr_route.h), and a flushed packet reaches the emit
+ * callback as at most two pieces: the bytes pending before the batch (when it has any), then its lines
+ * as one run of the slot's arena, valid until the emit callback and the flush callback after it have
+ * returned; the downstream's new pending buffer is one copy out of the arena. Packets, counters, log
+ * lines and their order are the same either way. Off by default. Returns 0, -EINVAL, -EBUSY (a batch is
+ * in flight: drain first). */
+int sr_core_set_payloads(sr_core *core, int on);
+
 /* Test hook (fault injection; nothing calls it in the executable): the fail_submit-th call of
  * sr_core_submit* fails as a failed sr_route_pack_submit (the batch is not taken), and the
  * fail_finish-th batch to complete fails as a failed sr_route_pack_result (its packets and log lines

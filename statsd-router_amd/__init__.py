@@ -54,6 +54,7 @@ ABI_FUNCTIONS = (
     "sr_comm_id", "sr_comm_open", "sr_comm_close", "sr_exchange_sizes", "sr_exchange_data",
     "sr_exchange_plan", "sr_exchange_run", "sr_exchange_rebase", "sr_route_pack_submit", "sr_route_pack_result",
     "sr_set_trace", "sr_route_pack_trace", "sr_set_knob", "sr_route_pack_many", "sr_regroup_run",
+    "sr_pack_payloads_many", "sr_pack_payloads", "sr_set_payloads", "sr_route_pack_payloads",
 )
 SR_MAX_PACK_DOWNSTREAMS = 4096
 SR_LAYOUT_AUTO, SR_LAYOUT_UNIFORM, SR_LAYOUT_SEGMENTS, SR_LAYOUT_CHUNKS = 0, 1, 2, 3
@@ -77,6 +78,13 @@ def pack_capacity(nbytes: int) -> int:
     """SR_PACK_CAPACITY: packed-bytes room that always suffices for a batch of nbytes."""
     return nbytes + nbytes // 2 + 4
 SR_MAX_BATCHES_PER_LAUNCH = 32
+PENDING_STRIDE = 1456   # SR_PENDING_STRIDE: one downstream's pending slot (1450 rounded up to 16)
+
+
+def payload_capacity(nbytes: int, n_downstreams: int) -> int:
+    """SR_PAYLOAD_CAPACITY: arena room that always suffices (every byte of the batch once, plus at most
+    1450 pending bytes per downstream)."""
+    return nbytes + SR_DOWNSTREAM_BUF_SIZE * n_downstreams
 
 
 class SrBatch(ctypes.Structure):
@@ -95,6 +103,17 @@ class SrPackBatch(ctypes.Structure):
         ("d_fill_in", ctypes.c_void_p), ("d_probed_dead", ctypes.c_void_p), ("d_sorted", ctypes.c_void_p),
         ("d_packets", ctypes.c_void_p), ("max_packets", ctypes.c_size_t), ("d_counts", ctypes.c_void_p),
         ("d_fill_out", ctypes.c_void_p),
+    ]
+
+
+class SrPayloadBatch(ctypes.Structure):
+    """struct sr_payload_batch (include/sr_route.h): one batch of sr_pack_payloads_many."""
+    _fields_ = [
+        ("d_bytes", ctypes.c_void_p), ("nbytes", ctypes.c_size_t), ("d_sorted", ctypes.c_void_p),
+        ("max_records", ctypes.c_size_t), ("d_packets", ctypes.c_void_p), ("max_packets", ctypes.c_size_t),
+        ("d_counts", ctypes.c_void_p), ("d_fill_out", ctypes.c_void_p), ("d_pend_in", ctypes.c_void_p),
+        ("d_pend_out", ctypes.c_void_p), ("d_payload", ctypes.c_void_p), ("payload_cap", ctypes.c_size_t),
+        ("d_offsets", ctypes.c_void_p), ("d_total", ctypes.c_void_p),
     ]
 
 
@@ -210,6 +229,10 @@ def _load_route_lib() -> ctypes.CDLL:
         "sr_route_pack_trace": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(vp), c_size_p]),
         "sr_set_knob": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int64]),
         "sr_route_pack_many": (ctypes.c_int, [vp, ctypes.POINTER(SrBatch), ctypes.POINTER(SrPackBatch), ctypes.c_size_t]),
+        "sr_pack_payloads_many": (ctypes.c_int, [vp, ctypes.POINTER(SrPayloadBatch), ctypes.c_size_t]),
+        "sr_pack_payloads": (ctypes.c_int, [vp, ctypes.POINTER(SrPayloadBatch)]),
+        "sr_set_payloads": (ctypes.c_int, [vp, ctypes.c_int]),
+        "sr_route_pack_payloads": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(vp), c_size_p]),
         "sr_regroup_run": (ctypes.c_int, [vp, ctypes.POINTER(SrTransport), _SIZES_FN, ctypes.c_int, ctypes.c_int,
                                           ctypes.POINTER(SrBatch), ctypes.c_size_t, vp, vp, vp, ctypes.c_size_t, vp, vp,
                                           ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp]),
@@ -379,6 +402,44 @@ class Router:
         recs = np.frombuffer((ctypes.c_uint8 * (8 * k)).from_address(r.value), dtype=RECORD_DTYPE).copy()
         hs = np.frombuffer((ctypes.c_uint8 * (8 * k)).from_address(h.value), dtype=np.uint64).copy()
         return recs, hs
+
+    def set_payloads(self, on: bool = True) -> None:
+        """sr_set_payloads: later route + pack submissions also gather the packets' bytes (room left for
+        each packet's carry) into the slot's page-locked memory."""
+        _check(self._lib.sr_set_payloads(self._h, 1 if on else 0), "sr_set_payloads")
+
+    def route_pack_payloads(self, slot: int):
+        """sr_route_pack_payloads after route_pack_result(slot) (slot 2: the last route_pack): (arena bytes
+        [offsets[-1]], offsets u32 [n_packets + 1]), copied."""
+        a, o, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        _check(self._lib.sr_route_pack_payloads(self._h, slot, ctypes.byref(a), ctypes.byref(o), ctypes.byref(n)),
+               "sr_route_pack_payloads")
+        offs = np.frombuffer((ctypes.c_uint8 * (4 * (n.value + 1))).from_address(o.value), dtype=np.uint32).copy()
+        total = int(offs[-1])
+        arena = (np.frombuffer((ctypes.c_uint8 * total).from_address(a.value), dtype=np.uint8).copy() if total
+                 else np.zeros(0, np.uint8))
+        return arena, offs
+
+    @staticmethod
+    def payload_batches(batches):
+        """The sr_payload_batch array of [(d_bytes, nbytes, d_sorted, max_records, d_packets, max_packets,
+        d_counts, d_fill_out, d_pend_in, d_pend_out, d_payload, payload_cap, d_offsets, d_total), ...]
+        (raw device pointers, 0 = NULL; reusable)."""
+        arr = (SrPayloadBatch * max(len(batches), 1))()
+        for i, b in enumerate(batches):
+            arr[i] = SrPayloadBatch(*[x if j in (1, 3, 5, 11) else (x or None) for j, x in enumerate(b)])
+        return arr
+
+    def pack_payloads_many(self, batches) -> None:
+        """sr_pack_payloads_many: the packets' bytes of packed batches (batches as payload_batches takes
+        them, or its array), asynchronous on the context's stream."""
+        arr = batches if isinstance(batches, ctypes.Array) else self.payload_batches(batches)
+        _check(self._lib.sr_pack_payloads_many(self._h, arr, len(batches)), "sr_pack_payloads_many")
+
+    def pack_payloads(self, batch) -> None:
+        """sr_pack_payloads: pack_payloads_many for one batch (a tuple as payload_batches takes them)."""
+        arr = self.payload_batches([batch])
+        _check(self._lib.sr_pack_payloads(self._h, arr), "sr_pack_payloads")
 
     def last_layout(self) -> int:
         """sr_last_layout: the lane layout of the context's last route launch (1 uniform, 2 segments,

@@ -68,6 +68,7 @@ def router_lib() -> ctypes.CDLL:
         L.sr_core_context.restype, L.sr_core_context.argtypes = vp, [vp]
         L.sr_core_inject_faults.restype = ctypes.c_int
         L.sr_core_inject_faults.argtypes = [vp, ctypes.c_uint, ctypes.c_uint]
+        L.sr_core_set_payloads.restype, L.sr_core_set_payloads.argtypes = ctypes.c_int, [vp, ctypes.c_int]
         _RLIB = L
     return _RLIB
 
@@ -83,6 +84,7 @@ class Core:
         self.packets: dict[int, list[bytes]] = {}
         self.logs: list[tuple[int, bytes]] = []
         self.flushes = 0
+        self.emit_iovecs: list[int] = []   # pieces of every emitted packet, in emit order
         hosts = (ctypes.c_char_p * n_downstreams)(*[h.encode() for h in ds_hosts])
         ports = (ctypes.c_char_p * n_downstreams)(*[p.encode() for p in ds_data_ports])
         self._keep = (hosts, ports, ping_prefix.encode(), hostname.encode())
@@ -92,6 +94,7 @@ class Core:
         def emit(_u, ds, iov, cnt, nbytes):
             b = b"".join(ctypes.string_at(iov[i].base, iov[i].len) for i in range(cnt))
             assert len(b) == nbytes
+            self.emit_iovecs.append(int(cnt))
             self.packets.setdefault(int(ds), []).append(b)
 
         def log(_u, level, msg, n):
@@ -164,6 +167,11 @@ class Core:
     def inject_faults(self, fail_submit: int = 0, fail_finish: int = 0) -> None:
         """sr_core_inject_faults (test hook)."""
         _check(self._L.sr_core_inject_faults(self._h, fail_submit, fail_finish), "sr_core_inject_faults")
+
+    def set_payloads(self, on: bool = True) -> None:
+        """sr_core_set_payloads: later batches' packets come from the device's arena (at most two pieces
+        per emitted packet)."""
+        _check(self._L.sr_core_set_payloads(self._h, 1 if on else 0), "sr_core_set_payloads")
 
     def set_layout(self, layout: int) -> None:
         """sr_set_layout on the core's device context (sr_core_context)."""

@@ -17,6 +17,7 @@
 #include "../../include/sr_route.h"
 #include "exchange.hpp"
 #include "mtu_kernel.hpp"
+#include "payload_kernel.hpp"
 #include "regroup_kernel.hpp"
 #include "route_host.hpp"
 
@@ -61,6 +62,7 @@ struct sr_ctx {
     int fill_cur;                 // region of d_fill holding the last submission's output (0 or 1)
     uint64_t *d_mcounts;          // 3 u64
     int trace;                    // sr_set_trace: submissions also return input-order records + hashes
+    int payloads;                 // sr_set_payloads: submissions also return the packets' bytes
     // packing knobs (sr_set_knob): forced chunk lines (0: by shape), XCD-local chunks, chain walked in emit
     uint32_t mtu_chunk;
     int mtu_xcd, mtu_walk;
@@ -82,6 +84,10 @@ struct sr_ctx {
         uint8_t *thost, *tdev;
         size_t trec_cap;
         int traced;               // the batch in the slot was submitted with trace on
+        // sr_set_payloads: the packets' bytes, their offsets and the total (one more page-locked allocation)
+        uint8_t *phost, *pdev;
+        size_t pay_cap, poff_cap; // arena bytes; offsets - 1 (descriptors)
+        int payloaded;            // the batch in the slot was submitted with payloads on
     } slot[3];
 };
 
@@ -195,6 +201,7 @@ void sr_close(sr_ctx *c) {
     for (auto &sl : c->slot) {
         if (sl.host) (void)hipHostFree(sl.host);
         if (sl.thost) (void)hipHostFree(sl.thost);
+        if (sl.phost) (void)hipHostFree(sl.phost);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -290,6 +297,12 @@ int sr_set_knob(sr_ctx *c, int knob, int64_t v) {
 int sr_set_trace(sr_ctx *c, int on) {
     if (!c) return -EINVAL;
     c->trace = on ? 1 : 0;
+    return 0;
+}
+
+int sr_set_payloads(sr_ctx *c, int on) {
+    if (!c) return -EINVAL;
+    c->payloads = on ? 1 : 0;
     return 0;
 }
 
@@ -775,6 +788,70 @@ int sr_pack_packets(sr_ctx *c, const sr_record *d_recs, const uint64_t *d_n_reco
     return sr_pack_packets_many(c, &b, 1);
 }
 
+// The packets' bytes of packed batches (payload_kernel.hpp): the offsets' scan, the gather (one wave
+// per descriptor the batch can have) and, where a batch keeps its pending bytes on the device, the
+// pass-through of the downstreams without a descriptor. No scratch: nothing is allocated here.
+static int payloads_impl(sr_ctx *c, const sr_payload_batch *batches, size_t count) {
+    static_assert(SR_PENDING_STRIDE == kPendStride && SR_PENDING_STRIDE % 16 == 0 &&
+                      SR_PENDING_STRIDE >= SR_DOWNSTREAM_BUF_SIZE,
+                  "pending slot");
+    if (!c || !batches || count == 0 || count > (size_t)kPayMaxBatches) return -EINVAL;
+    const uint32_t nds = c->ds.nds;
+    if (nds > SR_MAX_PACK_DOWNSTREAMS) return -EINVAL;
+    PayLaunch L;
+    memset(&L, 0, sizeof(L));
+    uint32_t tiles = 0;
+    bool pend = false;
+    for (size_t j = 0; j < count; ++j) {
+        const sr_payload_batch &b = batches[j];
+        if (!b.d_counts || !b.d_offsets || !b.d_total || (nds && !b.d_fill_out)) return -EINVAL;
+        if ((b.nbytes && !b.d_bytes) || b.nbytes > 0xFFFFFFF0ull || b.max_records > 0xFFFFFFF0ull) return -EINVAL;
+        if ((b.max_records && !b.d_sorted) || (b.max_packets && !b.d_packets)) return -EINVAL;
+        if (b.payload_cap && !b.d_payload) return -EINVAL;
+        if (b.d_pend_out && (!b.d_pend_in || b.d_pend_out == b.d_pend_in)) return -EINVAL;
+        PayBatchArg &a = L.b[j];
+        a.bytes = b.d_bytes;
+        a.sorted = b.d_sorted;
+        a.packets = b.d_packets;
+        a.counts = b.d_counts;
+        a.fill_out = b.d_fill_out;
+        a.pend_in = b.d_pend_in;
+        a.pend_out = b.d_pend_out;
+        a.payload = b.d_payload;
+        a.offsets = b.d_offsets;
+        a.total = b.d_total;
+        a.payload_cap = b.payload_cap;
+        a.nbytes = (uint32_t)b.nbytes;
+        a.max_records = (uint32_t)b.max_records;
+        // never more descriptors than SR_MAX_PACKETS of the batch: the gather's grid
+        const uint64_t most = SR_MAX_PACKETS((uint64_t)b.nbytes, nds);
+        const uint64_t room = b.max_packets < most ? b.max_packets : most;
+        a.max_packets = (uint32_t)(b.max_packets > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : b.max_packets);
+        a.tile0 = tiles;
+        const uint64_t per = (uint64_t)kPayWaves * kPayPerWave;   // packets per workgroup
+        const uint64_t t = (room + per - 1) / per;
+        if (tiles + t > 0x7FFFFFFFull) return -EINVAL;
+        tiles += (uint32_t)t;
+        pend = pend || (b.d_pend_out && nds);
+    }
+    (void)hipSetDevice(c->device);
+    L.nb = (uint32_t)count;
+    L.nds = nds;
+    L.tiles = tiles;
+    hipLaunchKernelGGL(payload_offsets_kernel, dim3((uint32_t)count), dim3(1024), 0, c->stream, L);
+    if (tiles) hipLaunchKernelGGL(payload_copy_kernel, dim3(tiles), dim3(kPayBlock), 0, c->stream, L);
+    if (pend)
+        hipLaunchKernelGGL(payload_pending_kernel, dim3((nds + kPayWaves - 1) / kPayWaves, (uint32_t)count),
+                           dim3(kPayBlock), 0, c->stream, L);
+    return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+int sr_pack_payloads_many(sr_ctx *c, const sr_payload_batch *batches, size_t count) {
+    return payloads_impl(c, batches, count);
+}
+
+int sr_pack_payloads(sr_ctx *c, const sr_payload_batch *batch) { return payloads_impl(c, batch, 1); }
+
 static int grow(void **ptr, size_t *cap, size_t need, size_t elem) {
     if (need <= *cap) return 0;
     free_ptr(*ptr);
@@ -843,6 +920,29 @@ static int slot_trace_reserve(sr_ctx *c, int k, size_t nbytes) {
     return 0;
 }
 
+// sr_set_payloads: the slot's arena, offsets and total (grown, never shrunk; the slot is idle):
+// arena | offsets (descriptors + 1) | total
+static int slot_payload_reserve(sr_ctx *c, int k, size_t nbytes) {
+    sr_ctx::Slot &sl = c->slot[k];
+    const size_t cap = (size_t)SR_PAYLOAD_CAPACITY(nbytes, c->ds.nds), pk = (size_t)SR_MAX_PACKETS(nbytes, c->ds.nds);
+    if (sl.phost && cap <= sl.pay_cap && pk <= sl.poff_cap) return 0;
+    if (sl.phost) (void)hipHostFree(sl.phost);
+    sl.phost = sl.pdev = nullptr;
+    sl.pay_cap = sl.poff_cap = 0;
+    void *h = nullptr, *d = nullptr;
+    if (hipHostMalloc(&h, up256(cap) + up256((pk + 1) * sizeof(uint32_t)) + 256, hipHostMallocMapped) != hipSuccess)
+        return -ENOMEM;
+    if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
+        (void)hipHostFree(h);
+        return -EIO;
+    }
+    sl.phost = (uint8_t *)h;
+    sl.pdev = (uint8_t *)d;
+    sl.pay_cap = cap;
+    sl.poff_cap = pk;
+    return 0;
+}
+
 static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, const uint16_t *fill) {
     sr_ctx::Slot &sl = c->slot[k];
     if (sl.busy) return -EBUSY;
@@ -858,6 +958,7 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
     const size_t full = c->ds.max_batch, fullp = (size_t)SR_MAX_PACKETS(full, nds);
     if ((rc = slot_reserve(c, k, full))) return rc;
     if (c->trace && (rc = slot_trace_reserve(c, k, full))) return rc;
+    if (c->payloads && (rc = slot_payload_reserve(c, k, full))) return rc;
     const size_t cap = nbytes ? nbytes : 1;   // never more lines than bytes
     const size_t pcap = (size_t)SR_MAX_PACKETS(cap, nds);
     if ((rc = grow((void **)&c->d_out, &c->d_out_cap, full, sizeof(sr_record)))) return rc;
@@ -925,6 +1026,14 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
     hipLaunchKernelGGL(pack_out_kernel, dim3((uint32_t)(want < 1024 ? (want ? want : 1) : 1024)), dim3(256), 0,
                        c->stream, o);
     if (hipGetLastError() != hipSuccess) return -EIO;
+    sl.payloaded = c->payloads;
+    if (c->payloads) {   // the packets' bytes straight into the slot's page-locked memory; the host holds the carries
+        const size_t o_off = up256(sl.pay_cap), o_tot = o_off + up256((sl.poff_cap + 1) * sizeof(uint32_t));
+        const sr_payload_batch yb{c->d_in, nbytes, c->d_sorted, nbytes ? cap : 0, c->d_packets, pcap < sl.poff_cap ? pcap : sl.poff_cap,
+                                  c->d_mcounts, f_out, nullptr, nullptr, sl.pdev, sl.pay_cap,
+                                  (uint32_t *)(sl.pdev + o_off), (uint64_t *)(sl.pdev + o_tot)};
+        if ((rc = payloads_impl(c, &yb, 1))) return rc;
+    }
     if (hipEventRecord(sl.done, c->stream) != hipSuccess) return -EIO;
     sl.busy = 1;
     return 0;
@@ -955,6 +1064,18 @@ int sr_route_pack_trace(sr_ctx *c, int slot, const sr_record **records, const ui
     *n = (size_t)(nr < sl.trec_cap ? nr : sl.trec_cap);
     *records = (const sr_record *)sl.thost;
     *hashes = (const uint64_t *)(sl.thost + up256(sl.trec_cap * sizeof(sr_record)));
+    return 0;
+}
+
+int sr_route_pack_payloads(sr_ctx *c, int slot, const uint8_t **payload, const uint32_t **offsets, size_t *n) {
+    if (!c || !payload || !offsets || !n || slot < 0 || slot > 2) return -EINVAL;
+    const sr_ctx::Slot &sl = c->slot[slot];
+    if (sl.busy || !sl.payloaded || !sl.phost || !sl.counts) return -EBUSY;
+    const uint64_t np = sl.counts[0];
+    const size_t room = sl.pk_cap < sl.poff_cap ? sl.pk_cap : sl.poff_cap;
+    *n = (size_t)(np < room ? np : room);
+    *payload = sl.phost;
+    *offsets = (const uint32_t *)(sl.phost + up256(sl.pay_cap));
     return 0;
 }
 
