@@ -264,7 +264,8 @@ int sr_exchange_plan(int world, int rank, const uint64_t *h_sent, const uint64_t
 /* The transport an exchange runs on. sr_exchange_data uses RCCL (ncclSend/ncclRecv in one group, the
  * own chunk by hipMemcpyAsync, the rebase by a kernel, all on the context's stream); a host that moves
  * the chunks another way (tests: torch.distributed gloo over host memory) supplies its own. Every
- * callback returns 0 or a negative errno. tag 0 = line bytes, 1 = records (a send of `bytes` bytes to
+ * callback returns 0 or a negative errno. tag 0 = line bytes, 1 = records, 2 = a probed-dead bitmap row
+ * (sr_exchange_dead_run) (a send of `bytes` bytes to
  * `peer` matches that peer's recv of the same tag from this rank). rebase: add peers[p].recv_byte0 to
  * the offset of records [recv_line0, +recv_lines) of every source p. */
 typedef struct sr_transport {
@@ -487,6 +488,86 @@ int sr_pack_payloads(sr_ctx *ctx, const sr_payload_batch *batch);   /* count = 1
 int sr_set_payloads(sr_ctx *ctx, int on);
 int sr_route_pack_payloads(sr_ctx *ctx, int slot, const uint8_t **payload, const uint32_t **offsets,
                            size_t *n_packets);
+
+/* ---- owner side of the multi-GPU regroup: received lines into packets ------------------------------ */
+/* After sr_regroup_launch / sr_regroup_run the lines of the shards a GPU owns lie in d_recv_bytes /
+ * d_recv_recs: every source's chunk in source order 0, 1, ..., each chunk batch 0's lines, then batch
+ * 1's, in input order. The owner is the one data thread of those shards: per shard it first drops the
+ * pending buffer of every shard that ANY source's launch probed dead (find_downstream zeroes
+ * active_buffer_length of the dead downstreams it visits, sr-main.c:106), then pushes the received
+ * lines (push_to_downstream / ds_schedule_flush, sr-main.c:49-83). The drop comes first because a source
+ * with a newer alive snapshot may send lines to a shard that another source still probed dead: the old
+ * pending bytes go, the new lines stay. (A source that flags a shard sends it no lines, so placing every
+ * flagging source before every sending one is a valid serial order per shard.) Per launch:
+ *   route with sr_batch.d_probed_dead -> sr_regroup_launch -> sr_exchange_dead -> sr_owner_pack
+ *   -> copy of the arena to the host; sr_flush_pending on the flush tick (ds_flush_timer_cb).
+ *
+ * sr_exchange_dead_run: the launch's probed-dead bitmaps to every owner. d_all_dead is u64
+ *   [world][nwords], nwords = max(1, ceil(n_downstreams / 64)). One kernel on the context's stream ORs
+ *   batches[j].d_probed_dead (NULL: nothing) over the launch's `count` batches (0..
+ *   SR_MAX_BATCHES_PER_LAUNCH) into row `rank`; then, within one group_start / group_end, row `rank` is
+ *   sent to every peer q != rank and row q received from it, in rank order, nwords * 8 bytes each under
+ *   tag 2. world == 1 makes no transport call. Only group_start, group_end, send and recv of the
+ *   transport are used; a transport that moves the rows from the host first waits for the context's
+ *   stream. Returns 0, -EINVAL or the first callback error (every operation is posted even so).
+ * sr_exchange_dead: the same on RCCL (ncclSend / ncclRecv on the context's stream), asynchronous.
+ *   Collective: every rank of the comm calls it once per launch, after sr_regroup_launch. */
+int sr_exchange_dead_run(sr_ctx *ctx, const sr_transport *t, int world, int rank, const sr_batch *batches,
+                         size_t count, uint64_t *d_all_dead);
+int sr_exchange_dead(sr_ctx *ctx, sr_comm *comm, const sr_batch *batches, size_t count, uint64_t *d_all_dead);
+
+/* sr_owner_pack: one launch's receive buffer into packets (asynchronous on the context's stream).
+ * With dead = the column-OR of d_all_dead's rows and fill_eff[s] = 0 for s in dead, else d_fill_in[s], the
+ * outputs are those of sr_pack_packets(d_recv_recs, the sum of d_recv_counts[p][0], max_records,
+ * fill_eff, NULL, ...) and, with d_payload, of sr_pack_payloads on d_recv_bytes: a dropped shard's first
+ * packet has carry 0 and reads nothing of d_pend_in, and a dropped shard without lines leaves
+ * d_fill_out[s] = 0 bytes in its d_pend_out slot. One small kernel (the fold) writes the line total and
+ * fill_eff into memory of the context; the packing and the gather run unchanged. Shards this GPU does not
+ * own receive no lines and pass through (apart from the drop).
+ * Rules of sr_pack_packets (descriptors past max_packets not written: check d_counts[0]) and, with
+ * d_payload, of sr_pack_payloads (d_pend_out needs d_pend_in and must not be it, so consecutive launches
+ * alternate two pending buffers; SR_PAYLOAD_CAPACITY(recv_nbytes, n_downstreams) always suffices; check
+ * *d_total <= payload_cap). d_fill_out may be d_fill_in. world in 1..SR_MAX_OWNERS, n_downstreams <=
+ * SR_MAX_PACK_DOWNSTREAMS. The first call (or one with a larger max_records) allocates scratch: not
+ * inside stream capture. Returns 0, -EINVAL, -ENOMEM, -EIO. */
+typedef struct sr_owner_batch {
+    const uint8_t *d_recv_bytes;   /* the receive buffers of sr_regroup_launch                           */
+    size_t recv_nbytes;            /* host value: the sum of h_received's bytes                          */
+    const sr_record *d_recv_recs;
+    size_t max_records;            /* room of d_recv_recs and of d_sorted                                */
+    const uint64_t *d_recv_counts; /* u64 [world][2] {lines, bytes} per source                           */
+    int world;
+    const uint64_t *d_all_dead;    /* NULL (nothing dropped) or u64 [world][nwords] (sr_exchange_dead)   */
+    const uint16_t *d_fill_in;     /* NULL (nothing pending) or n_downstreams u16                        */
+    sr_record *d_sorted;           /* as sr_pack_packets from here on                                    */
+    sr_packet *d_packets;
+    size_t max_packets;
+    uint64_t *d_counts;            /* 3 u64: {descriptors, valid lines, lines}                           */
+    uint16_t *d_fill_out;
+    const uint8_t *d_pend_in;      /* as sr_payload_batch from here on (used only with d_payload)        */
+    uint8_t *d_pend_out;
+    uint8_t *d_payload;            /* NULL: descriptors only                                             */
+    size_t payload_cap;
+    uint32_t *d_offsets;           /* max_packets + 1                                                    */
+    uint64_t *d_total;
+} sr_owner_batch;
+int sr_owner_pack(sr_ctx *ctx, const sr_owner_batch *batch);
+
+/* sr_flush_pending: ds_flush_timer_cb (sr-main.c:194-204) for pending buffers that live on the device:
+ * every downstream s with d_fill[s] > 0, in downstream order, becomes one descriptor {first 0, nlines 0,
+ * shard s, length 0, carry d_fill[s], open 0} whose bytes are the first d_fill[s] bytes of slot s of
+ * d_pend (SR_PENDING_STRIDE apart). d_counts (3 u64) = {descriptors needed, 0, 0}; with n =
+ * min(d_counts[0], max_packets), d_offsets[i] is the exclusive prefix sum of carry over the n written
+ * descriptors, d_offsets[n] = *d_total, and arena bytes [d_offsets[i], d_offsets[i+1]) are packet i;
+ * nothing at or past min(total, payload_cap) is written. Then d_fill[s] = 0 for every downstream whose
+ * packet is whole in the arena; one cut off by max_packets or by payload_cap keeps its fill (flush again
+ * with more room: nothing is lost silently). SR_PAYLOAD_CAPACITY(0, n_downstreams) always suffices.
+ * Asynchronous on the context's stream; no scratch, so the call can be captured in a graph.
+ * n_downstreams <= SR_MAX_PACK_DOWNSTREAMS. Returns 0, -EINVAL (a null pointer where its room is not
+ * 0), -EIO. */
+int sr_flush_pending(sr_ctx *ctx, uint16_t *d_fill, const uint8_t *d_pend, sr_packet *d_packets,
+                     size_t max_packets, uint64_t *d_counts, uint8_t *d_payload, size_t payload_cap,
+                     uint32_t *d_offsets, uint64_t *d_total);
 
 /* Developer and test knobs of one context (A/B runs and tests only; the library reads no environment
  * variable and no knob changes any record, packet or count, only which kernels produce them):

@@ -55,6 +55,7 @@ ABI_FUNCTIONS = (
     "sr_exchange_plan", "sr_exchange_run", "sr_exchange_rebase", "sr_route_pack_submit", "sr_route_pack_result",
     "sr_set_trace", "sr_route_pack_trace", "sr_set_knob", "sr_route_pack_many", "sr_regroup_run",
     "sr_pack_payloads_many", "sr_pack_payloads", "sr_set_payloads", "sr_route_pack_payloads",
+    "sr_exchange_dead_run", "sr_exchange_dead", "sr_owner_pack", "sr_flush_pending",
 )
 SR_MAX_PACK_DOWNSTREAMS = 4096
 SR_LAYOUT_AUTO, SR_LAYOUT_UNIFORM, SR_LAYOUT_SEGMENTS, SR_LAYOUT_CHUNKS = 0, 1, 2, 3
@@ -114,6 +115,20 @@ class SrPayloadBatch(ctypes.Structure):
         ("d_counts", ctypes.c_void_p), ("d_fill_out", ctypes.c_void_p), ("d_pend_in", ctypes.c_void_p),
         ("d_pend_out", ctypes.c_void_p), ("d_payload", ctypes.c_void_p), ("payload_cap", ctypes.c_size_t),
         ("d_offsets", ctypes.c_void_p), ("d_total", ctypes.c_void_p),
+    ]
+
+
+class SrOwnerBatch(ctypes.Structure):
+    """struct sr_owner_batch (include/sr_route.h): one launch's receive buffer for sr_owner_pack. Device
+    pointers are plain integers (None / 0 = NULL); fields left out of the constructor are zero."""
+    _fields_ = [
+        ("d_recv_bytes", ctypes.c_void_p), ("recv_nbytes", ctypes.c_size_t), ("d_recv_recs", ctypes.c_void_p),
+        ("max_records", ctypes.c_size_t), ("d_recv_counts", ctypes.c_void_p), ("world", ctypes.c_int),
+        ("d_all_dead", ctypes.c_void_p), ("d_fill_in", ctypes.c_void_p), ("d_sorted", ctypes.c_void_p),
+        ("d_packets", ctypes.c_void_p), ("max_packets", ctypes.c_size_t), ("d_counts", ctypes.c_void_p),
+        ("d_fill_out", ctypes.c_void_p), ("d_pend_in", ctypes.c_void_p), ("d_pend_out", ctypes.c_void_p),
+        ("d_payload", ctypes.c_void_p), ("payload_cap", ctypes.c_size_t), ("d_offsets", ctypes.c_void_p),
+        ("d_total", ctypes.c_void_p),
     ]
 
 
@@ -236,6 +251,11 @@ def _load_route_lib() -> ctypes.CDLL:
         "sr_regroup_run": (ctypes.c_int, [vp, ctypes.POINTER(SrTransport), _SIZES_FN, ctypes.c_int, ctypes.c_int,
                                           ctypes.POINTER(SrBatch), ctypes.c_size_t, vp, vp, vp, ctypes.c_size_t, vp, vp,
                                           ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp]),
+        "sr_exchange_dead_run": (ctypes.c_int, [vp, ctypes.POINTER(SrTransport), ctypes.c_int, ctypes.c_int,
+                                                ctypes.POINTER(SrBatch), ctypes.c_size_t, vp]),
+        "sr_exchange_dead": (ctypes.c_int, [vp, vp, ctypes.POINTER(SrBatch), ctypes.c_size_t, vp]),
+        "sr_owner_pack": (ctypes.c_int, [vp, ctypes.POINTER(SrOwnerBatch)]),
+        "sr_flush_pending": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_size_t, vp, vp, ctypes.c_size_t, vp, vp]),
     }
     for name in ABI_FUNCTIONS:
         if os.environ.get("SR_ROUTE_LIB") and not hasattr(lib, name):
@@ -555,10 +575,12 @@ class Router:
 
     @staticmethod
     def owner_batches(batches):
-        """The sr_batch array of [(d_bytes, nbytes, d_recs, max_records, d_n_records), ...] (reusable)."""
+        """The sr_batch array of [(d_bytes, nbytes, d_recs, max_records, d_n_records[, d_probed_dead]), ...]
+        (reusable; the bitmap is what exchange_dead reads, the pack calls ignore it)."""
         arr = (SrBatch * max(len(batches), 1))()
-        for i, (db, nb, dr, mr, dn) in enumerate(batches):
-            arr[i] = SrBatch(db, nb, dr, mr, None, dn, None)
+        for i, b in enumerate(batches):
+            db, nb, dr, mr, dn = b[:5]
+            arr[i] = SrBatch(db, nb, dr, mr, None, dn, (b[5] or None) if len(b) > 5 else None)
         return arr
 
     _owner_batches = owner_batches
@@ -686,6 +708,46 @@ class Router:
         p = np.ascontiguousarray(peers, dtype=PEER_DTYPE)
         _check(self._lib.sr_exchange_rebase(self._h, ctypes.c_void_p(d_recv_recs), p.ctypes.data, int(p.size)),
                "sr_exchange_rebase")
+
+    def dead_words(self) -> int:
+        """Words of one probed-dead bitmap (a row of d_all_dead): max(1, ceil(n_downstreams / 64))."""
+        return max((self.n_downstreams + 63) // 64, 1)
+
+    def exchange_dead_run(self, transport: "Transport", world: int, rank: int, batches, d_all_dead: int) -> None:
+        """sr_exchange_dead_run: the launch's probed-dead bitmaps (batches as owner_batches takes them, with
+        d_probed_dead, or its array) ORed into row `rank` of d_all_dead (u64 [world, dead_words()]) and the
+        rows exchanged on a Python transport under tag 2."""
+        err = []
+        cb = _transport_struct(transport, err)
+        arr = batches if isinstance(batches, ctypes.Array) else self._owner_batches(batches)
+        rc = self._lib.sr_exchange_dead_run(self._h, ctypes.byref(cb), world, rank, arr, len(batches),
+                                            ctypes.c_void_p(d_all_dead))
+        if err:
+            raise err[0]
+        _check(rc, "sr_exchange_dead_run")
+
+    def exchange_dead(self, comm: "Comm", batches, d_all_dead: int) -> None:
+        """sr_exchange_dead: exchange_dead_run over the communicator (asynchronous on the router's stream;
+        collective)."""
+        arr = batches if isinstance(batches, ctypes.Array) else self._owner_batches(batches)
+        _check(self._lib.sr_exchange_dead(self._h, comm.handle, arr, len(batches), ctypes.c_void_p(d_all_dead)),
+               "sr_exchange_dead")
+
+    def owner_pack(self, batch: SrOwnerBatch | None = None, **fields) -> None:
+        """sr_owner_pack: one launch's receive buffer into packets (an SrOwnerBatch, or its fields by name),
+        asynchronous on the router's stream."""
+        b = batch if batch is not None else SrOwnerBatch(**{k: (v or None) if k.startswith("d_") else v
+                                                            for k, v in fields.items()})
+        _check(self._lib.sr_owner_pack(self._h, ctypes.byref(b)), "sr_owner_pack")
+
+    def flush_pending(self, d_fill: int, d_pend: int, d_packets: int, max_pk: int, d_counts: int, d_payload: int,
+                      payload_cap: int, d_offsets: int, d_total: int) -> None:
+        """sr_flush_pending: every non-empty pending slot on the device into one packet of the arena, its fill
+        reset (asynchronous on the router's stream; capturable)."""
+        vp = ctypes.c_void_p
+        _check(self._lib.sr_flush_pending(self._h, vp(d_fill or 0), vp(d_pend or 0), vp(d_packets or 0), max_pk,
+                                          vp(d_counts or 0), vp(d_payload or 0), payload_cap, vp(d_offsets or 0),
+                                          vp(d_total or 0)), "sr_flush_pending")
 
     def sync(self) -> None:
         _check(self._lib.sr_sync(self._h), "sr_sync")

@@ -17,6 +17,7 @@
 #include "../../include/sr_route.h"
 #include "exchange.hpp"
 #include "mtu_kernel.hpp"
+#include "owner_kernel.hpp"
 #include "payload_kernel.hpp"
 #include "regroup_kernel.hpp"
 #include "route_host.hpp"
@@ -61,6 +62,9 @@ struct sr_ctx {
     uint16_t *d_fill;             // [3][nds]: two chained outputs, then the uploaded fill of a submission
     int fill_cur;                 // region of d_fill holding the last submission's output (0 or 1)
     uint64_t *d_mcounts;          // 3 u64
+    // sr_owner_pack: the receive buffer's line total and the pending fills after the dead-downstream drop
+    uint64_t *d_owner_n;
+    uint16_t *d_owner_fill;       // [nds]
     int trace;                    // sr_set_trace: submissions also return input-order records + hashes
     int payloads;                 // sr_set_payloads: submissions also return the packets' bytes
     // packing knobs (sr_set_knob): forced chunk lines (0: by shape), XCD-local chunks, chain walked in emit
@@ -198,6 +202,8 @@ void sr_close(sr_ctx *c) {
     free_ptr(c->d_packets);
     free_ptr(c->d_fill);
     free_ptr(c->d_mcounts);
+    free_ptr(c->d_owner_n);
+    free_ptr(c->d_owner_fill);
     for (auto &sl : c->slot) {
         if (sl.host) (void)hipHostFree(sl.host);
         if (sl.thost) (void)hipHostFree(sl.thost);
@@ -1423,6 +1429,95 @@ int sr_exchange_rebase(sr_ctx *ctx, sr_record *d_recv_recs, const sr_exchange_pe
     if (a.n_lines && !d_recv_recs) return -EINVAL;
     (void)hipSetDevice(ctx->device);
     return rebase_launch(ctx->stream, d_recv_recs, peers, world);
+}
+
+// ---- owner side (owner_kernel.hpp) -----------------------------------------------------------------
+static uint32_t dead_words(const sr_ctx *c) { return c->ds.nds ? (c->ds.nds + 63u) / 64u : 1u; }
+
+// The launch's bitmaps ORed into row `rank` (one kernel), then the rows over the transport.
+static int exchange_dead_impl(sr_ctx *ctx, const sr_transport &t, int world, int rank, const sr_batch *batches,
+                              size_t count, uint64_t *d_all_dead) {
+    DeadOrArgs a;
+    memset(&a, 0, sizeof(a));
+    for (size_t j = 0; j < count; ++j) a.pd[j] = batches[j].d_probed_dead;
+    a.count = (uint32_t)count;
+    a.nwords = dead_words(ctx);
+    a.row = d_all_dead + (size_t)rank * a.nwords;
+    (void)hipSetDevice(ctx->device);
+    hipLaunchKernelGGL(owner_dead_or_kernel, dim3((a.nwords + 63u) / 64u), dim3(64), 0, ctx->stream, a);
+    if (hipGetLastError() != hipSuccess) return -EIO;
+    return exchange_dead_rows(t, world, rank, d_all_dead, a.nwords);
+}
+
+static bool exchange_dead_args_ok(const sr_ctx *ctx, int world, int rank, const sr_batch *batches, size_t count,
+                                  const uint64_t *d_all_dead) {
+    return ctx && d_all_dead && world >= 1 && world <= (int)kMaxOwners && rank >= 0 && rank < world &&
+           count <= SR_MAX_BATCHES_PER_LAUNCH && (count == 0 || batches);
+}
+
+int sr_exchange_dead_run(sr_ctx *ctx, const sr_transport *t, int world, int rank, const sr_batch *batches,
+                         size_t count, uint64_t *d_all_dead) {
+    if (!t || !exchange_dead_args_ok(ctx, world, rank, batches, count, d_all_dead)) return -EINVAL;
+    if (world > 1 && (!t->group_start || !t->group_end || !t->send || !t->recv)) return -EINVAL;
+    return exchange_dead_impl(ctx, *t, world, rank, batches, count, d_all_dead);
+}
+
+int sr_exchange_dead(sr_ctx *ctx, sr_comm *comm, const sr_batch *batches, size_t count, uint64_t *d_all_dead) {
+    if (!comm || !exchange_dead_args_ok(ctx, comm->world, comm->rank, batches, count, d_all_dead)) return -EINVAL;
+    RcclApi *r = rccl_api();
+    if (!r) return -ENOSYS;
+    RcclTransport rt{r, comm, ctx->stream, ctx};
+    const sr_transport t{&rt, rccl_group_start, rccl_group_end, rccl_send, rccl_recv, rccl_copy, rccl_rebase};
+    return exchange_dead_impl(ctx, t, comm->world, comm->rank, batches, count, d_all_dead);
+}
+
+// The fold, then the packing and the gather as sr_pack_packets / sr_pack_payloads run them: every argument
+// is checked before the first launch, so that -EINVAL leaves nothing enqueued.
+int sr_owner_pack(sr_ctx *c, const sr_owner_batch *b) {
+    if (!c || !b || !b->d_recv_counts || b->world < 1 || b->world > (int)kMaxOwners) return -EINVAL;
+    const uint32_t nds = c->ds.nds;
+    if (nds > SR_MAX_PACK_DOWNSTREAMS) return -EINVAL;
+    if (!b->d_counts || (nds && !b->d_fill_out) || b->max_records > 0xFFFFFFF0ull) return -EINVAL;
+    if (b->max_records && (!b->d_recv_recs || !b->d_sorted)) return -EINVAL;
+    if (b->max_packets && !b->d_packets) return -EINVAL;
+    if (b->d_payload) {   // sr_pack_payloads' rules
+        if (!b->d_offsets || !b->d_total) return -EINVAL;
+        if ((b->recv_nbytes && !b->d_recv_bytes) || b->recv_nbytes > 0xFFFFFFF0ull) return -EINVAL;
+        if (b->d_pend_out && (!b->d_pend_in || b->d_pend_out == b->d_pend_in)) return -EINVAL;
+    }
+    (void)hipSetDevice(c->device);
+    if (!c->d_owner_n && hipMalloc(&c->d_owner_n, sizeof(uint64_t)) != hipSuccess) return -ENOMEM;
+    if (!c->d_owner_fill && hipMalloc(&c->d_owner_fill, (nds ? nds : 1) * sizeof(uint16_t)) != hipSuccess)
+        return -ENOMEM;
+    const OwnerFoldArgs f{b->d_recv_counts, b->d_all_dead, b->d_fill_in, c->d_owner_n, c->d_owner_fill,
+                          (uint32_t)b->world, nds, dead_words(c)};
+    hipLaunchKernelGGL(owner_fold_kernel, dim3(1), dim3(kOwnerBlock), 0, c->stream, f);
+    if (hipGetLastError() != hipSuccess) return -EIO;
+    const sr_pack_batch pb{b->d_recv_recs, c->d_owner_n, b->max_records, c->d_owner_fill, nullptr,
+                           b->d_sorted, b->d_packets, b->max_packets, b->d_counts, b->d_fill_out};
+    int rc = pack_many_impl(c, &pb, 1, nullptr, nullptr);
+    if (rc || !b->d_payload) return rc;
+    const sr_payload_batch yb{b->d_recv_bytes, b->recv_nbytes, b->d_sorted, b->max_records, b->d_packets,
+                              b->max_packets, b->d_counts, b->d_fill_out, b->d_pend_in, b->d_pend_out,
+                              b->d_payload, b->payload_cap, b->d_offsets, b->d_total};
+    return payloads_impl(c, &yb, 1);
+}
+
+int sr_flush_pending(sr_ctx *c, uint16_t *d_fill, const uint8_t *d_pend, sr_packet *d_packets, size_t max_packets,
+                     uint64_t *d_counts, uint8_t *d_payload, size_t payload_cap, uint32_t *d_offsets,
+                     uint64_t *d_total) {
+    if (!c || !d_counts || !d_offsets || !d_total) return -EINVAL;
+    const uint32_t nds = c->ds.nds;
+    if (nds > SR_MAX_PACK_DOWNSTREAMS) return -EINVAL;
+    if ((nds && (!d_fill || !d_pend)) || (max_packets && !d_packets) || (payload_cap && !d_payload)) return -EINVAL;
+    const uint32_t room = (uint32_t)(max_packets < nds ? max_packets : nds);   // never more descriptors than slots
+    const FlushArgs a{d_fill, d_pend, d_packets, d_counts, d_payload, d_offsets, d_total, payload_cap, nds, room};
+    (void)hipSetDevice(c->device);
+    hipLaunchKernelGGL(flush_scan_kernel, dim3(1), dim3(kOwnerBlock), 0, c->stream, a);
+    if (room)
+        hipLaunchKernelGGL(flush_copy_kernel, dim3((room + kPayWaves - 1) / kPayWaves), dim3(kPayBlock), 0,
+                           c->stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -EIO;
 }
 
 }  // extern "C"

@@ -312,3 +312,77 @@ class LaunchRegrouper:
                                       rb.data_ptr(), rr.data_ptr())
         self.last_sent, self.last_received = sent.astype(np.int64).tolist(), received.astype(np.int64).tolist()
         return rb[:n_b], rr[:n_l], rc
+
+
+class OwnerPacker:
+    """The owner side of one launch on one router context: sr_exchange_dead(_run), sr_owner_pack into
+    buffers of its own, sr_flush_pending. The pending fills and bytes stay on the device in two buffers
+    that alternate between launches (sr_pack_payloads' rule: d_pend_out is never d_pend_in); `cur` is the
+    pair holding the state after the last call. All work goes on the router's stream; the tensors are
+    allocated on torch's current one, so the caller orders the two (the tests synchronise).
+    poison: a byte every output buffer is refilled with before each call (tests compare them whole)."""
+
+    def __init__(self, pkg, router, world: int, max_records: int, max_bytes: int, max_packets: int | None = None,
+                 payload_cap: int | None = None, poison: int | None = None, slack: int = 64):
+        self.pkg, self.router, self.world, self.poison, self.slack = pkg, router, world, poison, slack
+        n = self.n = router.n_downstreams
+        dev = torch.device("cuda", router.device)
+        self.max_records = max(max_records, 1)
+        self.mp = pkg.max_packets(max_bytes, n) if max_packets is None else max_packets
+        self.pcap = pkg.payload_capacity(max_bytes, n) if payload_cap is None else payload_cap
+        z = lambda k, dt: torch.zeros(max(k, 1), dtype=dt, device=dev)
+        self.fill = [z(n, torch.int16), z(n, torch.int16)]
+        self.pend = [z(n * pkg.PENDING_STRIDE, torch.uint8), z(n * pkg.PENDING_STRIDE, torch.uint8)]
+        self.cur = 0
+        self.all_dead = z(world * router.dead_words(), torch.int64)
+        self.sorted = z(self.max_records, torch.int64)
+        self.packets = z(2 * (self.mp + 1), torch.int64)
+        self.counts = z(3, torch.int64)
+        self.arena = z(self.pcap + slack, torch.uint8)
+        self.offsets = z(4 * (self.mp + 1) + slack, torch.uint8)
+        self.total = z(1, torch.int64)
+
+    def set_pending(self, fills, image) -> None:
+        """The state before the first launch: n fills (u16) and the n pending slots' bytes."""
+        f = np.zeros(max(self.n, 1), dtype=np.uint16)
+        f[: self.n] = np.asarray(fills, dtype=np.uint16)
+        self.fill[self.cur].copy_(torch.from_numpy(f.view(np.int16).copy()))
+        self.pend[self.cur].copy_(torch.from_numpy(np.ascontiguousarray(image, dtype=np.uint8)))
+
+    def _refill(self, *tensors) -> None:
+        if self.poison is not None:
+            for t in tensors:
+                t.view(torch.uint8).fill_(self.poison)
+            torch.cuda.synchronize(self.arena.device)
+
+    def exchange_dead(self, via, rank: int, batches) -> None:
+        """The launch's probed-dead bitmaps into all_dead: `via` is a pkg.Comm or a pkg.Transport."""
+        self._refill(self.all_dead)
+        if isinstance(via, self.pkg.Comm):
+            self.router.exchange_dead(via, batches, self.all_dead.data_ptr())
+        else:
+            self.router.exchange_dead_run(via, self.world, rank, batches, self.all_dead.data_ptr())
+
+    def pack(self, d_recv_bytes: int, recv_nbytes: int, d_recv_recs: int, d_recv_counts: int, dead: bool = True,
+             payload: bool = True) -> None:
+        """sr_owner_pack of one receive buffer from the current pending pair into the other one."""
+        i, o = self.cur, 1 - self.cur
+        self._refill(self.fill[o], self.pend[o], self.sorted, self.packets, self.counts, self.arena, self.offsets,
+                     self.total)
+        self.router.owner_pack(
+            d_recv_bytes=d_recv_bytes, recv_nbytes=recv_nbytes, d_recv_recs=d_recv_recs, max_records=self.max_records,
+            d_recv_counts=d_recv_counts, world=self.world, d_all_dead=self.all_dead.data_ptr() if dead else 0,
+            d_fill_in=self.fill[i].data_ptr(), d_sorted=self.sorted.data_ptr(), d_packets=self.packets.data_ptr(),
+            max_packets=self.mp, d_counts=self.counts.data_ptr(), d_fill_out=self.fill[o].data_ptr(),
+            d_pend_in=self.pend[i].data_ptr(), d_pend_out=self.pend[o].data_ptr(),
+            d_payload=self.arena.data_ptr() if payload else 0, payload_cap=self.pcap,
+            d_offsets=self.offsets.data_ptr(), d_total=self.total.data_ptr())
+        self.cur = o
+
+    def flush(self) -> None:
+        """sr_flush_pending of the current pending pair into the arena."""
+        self._refill(self.packets, self.counts, self.arena, self.offsets, self.total)
+        c = self.cur
+        self.router.flush_pending(self.fill[c].data_ptr(), self.pend[c].data_ptr(), self.packets.data_ptr(), self.mp,
+                                  self.counts.data_ptr(), self.arena.data_ptr(), self.pcap, self.offsets.data_ptr(),
+                                  self.total.data_ptr())
