@@ -31,10 +31,7 @@
 
 namespace srk {
 
-constexpr unsigned KV_CHUNKS = 8388608u;       // the chunk-layout kernel (route_chunk_kernel)
-// developer ablations of route_chunk_kernel (timing / counter attribution only, wrong records; built
-// with -DSR_CHUNK_ABL=<mask> into tools/ab, never shipped)
-enum : unsigned { CH_ABL_NO_U = 1u << 24, CH_ABL_NO_SUF = 1u << 25, CH_ABL_NO_EMIT = 1u << 26 };
+// (KV_CHUNKS and the CH_ABL_* developer ablations: the variant mask in route_kernel.hpp)
 constexpr int kCinv = 65;                      // K^-z, z = 0 .. 64
 constexpr int kCpowEntries = kCinv + 2 * 256;  // + K^(64 (255 - l)), K^-(64 (255 - l)) per lane l
 constexpr uint32_t kFlagTail = 1u;             // tail granules (flag field of mk_status)
@@ -161,7 +158,7 @@ __global__ __launch_bounds__(256, 7) __attribute__((amdgpu_waves_per_eu(7, 8))) 
             sm.scan_total = 0;
         }
         wg_barrier();
-        scan_batch_split<256, ABL>(p, p.b[blockIdx.x], ep0, sm, wave, lane);
+        scan_batch_split<ABL>(p, p.b[blockIdx.x], ep0, sm, wave, lane);
         if (tid == 64) arrive(p, blockIdx.x, ep0);
         return;
     }

@@ -113,7 +113,7 @@ struct DeviceState {
         max_batch = max_batch_bytes;
         nds = n_downstreams;
         nwords = (n_downstreams + 63) / 64;
-        // status granules for kMaxBatches batches of the smallest tile (256 threads, 16 KiB)
+        // status granules for kMaxBatches batches of 16 KiB tiles
         max_tiles = (uint32_t)(kMaxBatches * ((max_batch_bytes + 16383) / 16384));
         h_alive = (uint64_t *)calloc(nwords ? nwords : 1, sizeof(uint64_t));
         if (!h_alive) return -ENOMEM;
@@ -365,15 +365,15 @@ struct DeviceState {
 // Launch the route kernel over the batches of p (tile ranges assigned here; empty batches get a
 // zero line count without a kernel). With more than kOverlay dead shards every batch is launched
 // on its own so that the deferred-probe list holds one batch at a time.
-template <int BLOCK, unsigned ABL>
+template <unsigned ABL>
 inline int launch_route(DeviceState &ds, const RouteParams &in, hipStream_t stream) {
-    constexpr uint64_t T = (uint64_t)BLOCK * kLaneBytes;
+    constexpr uint64_t T = kTile;
     if (ds.wide() && in.nb > 1) {
         for (uint32_t i = 0; i < in.nb; ++i) {
             RouteParams one = in;
             one.nb = 1;
             one.b[0] = in.b[i];
-            const int rc = launch_route<BLOCK, ABL>(ds, one, stream);
+            const int rc = launch_route<ABL>(ds, one, stream);
             if (rc) return rc;
         }
         return 0;
@@ -397,7 +397,7 @@ inline int launch_route(DeviceState &ds, const RouteParams &in, hipStream_t stre
     }
     if (p.nb == 0) return 0;
     // 8+ batches: each batch's tiles on one XCD class; its scanner (block j) shares that class
-    const bool xl = !(ABL & ABL_NO_XCD_LOCAL) && p.nb >= 8;
+    const bool xl = p.nb >= 8;
     p.xcd_local = xl ? 1u : 0u;
     uint32_t cls_tiles[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t sb = 0;
@@ -502,11 +502,10 @@ inline int launch_route(DeviceState &ds, const RouteParams &in, hipStream_t stre
                                !(ABL & KV_CHUNKS);
     ds.last_marks_pending = slots_to_pack;
     if constexpr ((ABL & KV_CHUNKS) != 0) {
-        static_assert(BLOCK == 256, "route_chunk_kernel: 256 lanes of 64 bytes per 16 KiB tile");
         // its probe stops after the first picks: with two or more dead shards it needs the deferral
         // (no scratch for it, e.g. inside a stream capture: the uniform kernel probes in full)
         if (ds.dead >= 2 && ds.dead < ds.nds && !p.defer)
-            hipLaunchKernelGGL((route_kernel<BLOCK, KV_UNIFORM>), dim3(p.total_blocks), dim3(BLOCK), 0, stream, p);
+            hipLaunchKernelGGL((route_kernel<kBlock, KV_UNIFORM>), dim3(p.total_blocks), dim3(kBlock), 0, stream, p);
         else if (defer1)
             hipLaunchKernelGGL((route_chunk_kernel<kD1>), dim3(p.total_blocks), dim3(256), 0, stream, p);
         else if (dead1)
@@ -516,17 +515,17 @@ inline int launch_route(DeviceState &ds, const RouteParams &in, hipStream_t stre
     } else if constexpr ((ABL & KV_PICKS) != 0) {
         // the picks-only variant needs the deferral once two or more shards are dead
         if (ds.dead >= 2 && ds.dead < ds.nds && !p.defer)
-            hipLaunchKernelGGL((route_kernel<BLOCK, (ABL & ~KV_PICKS)>), dim3(p.total_blocks), dim3(BLOCK), 0, stream, p);
+            hipLaunchKernelGGL((route_kernel<kBlock, (ABL & ~KV_PICKS)>), dim3(p.total_blocks), dim3(kBlock), 0, stream, p);
         else if (defer1)
-            hipLaunchKernelGGL((route_kernel<BLOCK, kD1>), dim3(p.total_blocks), dim3(BLOCK), 0, stream, p);
+            hipLaunchKernelGGL((route_kernel<kBlock, kD1>), dim3(p.total_blocks), dim3(kBlock), 0, stream, p);
         else if (dead1 && p.hist)
-            hipLaunchKernelGGL((route_kernel<BLOCK, kK1 | KV_HIST1>), dim3(p.total_blocks), dim3(BLOCK), 0, stream, p);
+            hipLaunchKernelGGL((route_kernel<kBlock, kK1 | KV_HIST1>), dim3(p.total_blocks), dim3(kBlock), 0, stream, p);
         else if (dead1)
-            hipLaunchKernelGGL((route_kernel<BLOCK, kK1>), dim3(p.total_blocks), dim3(BLOCK), 0, stream, p);
+            hipLaunchKernelGGL((route_kernel<kBlock, kK1>), dim3(p.total_blocks), dim3(kBlock), 0, stream, p);
         else
-            hipLaunchKernelGGL((route_kernel<BLOCK, ABL>), dim3(p.total_blocks), dim3(BLOCK), 0, stream, p);
+            hipLaunchKernelGGL((route_kernel<kBlock, ABL>), dim3(p.total_blocks), dim3(kBlock), 0, stream, p);
     } else {
-        hipLaunchKernelGGL((route_kernel<BLOCK, ABL>), dim3(p.total_blocks), dim3(BLOCK), 0, stream, p);
+        hipLaunchKernelGGL((route_kernel<kBlock, ABL>), dim3(p.total_blocks), dim3(kBlock), 0, stream, p);
     }
     if (hipGetLastError() != hipSuccess) return -EIO;
     // the key histograms exist only where route_kernel counted them: every shard alive, or exactly one

@@ -33,10 +33,11 @@
 //   * Lines, in windows of 256 tile-local lines: (end, first ':') staged in LDS, then every line
 //     hashed from the LDS image: sdbm with SDWA byte-pair products and one 64x64 multiply per 8
 //     bytes (sdbm_img), a name of n bytes being ceil(n/64) 64-byte segments combined with K^len.
-//     Two lane layouts, one instantiation each (identical records): KV_UNIFORM gives every line of
-//     a tile the same G lanes (from the tile's mean line length); KV_SEGMENTS gives a tile of mixed
-//     lengths one lane per segment, lines packed back to back over the lanes, a line's hash the
-//     difference of an inclusive wave scan of segment hashes (route_host.hpp picks per launch).
+//     Two lane layouts (identical records): KV_UNIFORM gives every line of a tile the same G lanes
+//     (from the tile's mean line length); KV_SEGMENTS gives a tile of mixed lengths one lane per
+//     segment, lines packed back to back over the lanes, a line's hash the difference of an
+//     inclusive wave scan of segment hashes. (A third layout, KV_CHUNKS, is route_chunk_kernel in
+//     chunk_kernel.hpp.)
 //   * Shard pick: h % N through a 64-bit magic reciprocal when every shard is alive; otherwise the
 //     reference's probe: its first two picks here (reciprocals and alive words in LDS pad dwords),
 //     a line needing a third deferred by record index to probe_defer_kernel (16-entry register
@@ -48,6 +49,20 @@
 //     all arrivals and advances the context's epoch, so stale granules of earlier launches are never
 //     mistaken for current ones, with or without graph replay.
 // No MFMA: HBM-bound byte work on VALU + LDS.
+//
+// Variants. The kernels' template argument is a mask of the KV_* bits below (ABL_* bits join them in
+// developer builds only). All variants write identical records; the library holds 12 instantiations of
+// route_kernel and 4 of route_chunk_kernel. For each lane layout L of KV_UNIFORM and KV_SEGMENTS:
+//     L | KV_ALIVE                           every shard alive
+//     L | KV_PICKS                           dead shards, probes past the first picks deferred
+//     L | KV_PICKS | KV_DEFER1               two or more of at most 64 dead, one pick then the deferral
+//     L | KV_PICKS | KV_DEAD1                exactly one dead shard
+//     L | KV_PICKS | KV_DEAD1 | KV_HIST1     ... in a route + pack launch (tile histograms)
+//     L                                      the full probe: two or more dead and nothing to defer to
+// and KV_CHUNKS, KV_CHUNKS | KV_ALIVE, KV_CHUNKS | KV_DEFER1, KV_CHUNKS | KV_DEAD1.
+// Who picks: launch_product (sr_route.hip) takes the layout from DeviceState::choose_segments and
+// KV_ALIVE or KV_PICKS from the alive snapshot's dead count; launch_route (route_host.hpp) then narrows
+// a KV_PICKS or KV_CHUNKS launch to KV_DEFER1, KV_DEAD1 (| KV_HIST1) or the full probe, per launch.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -70,50 +85,65 @@ constexpr uint64_t K = 65599ull;             // sdbm multiplier: (h<<6)+(h<<16)-
 constexpr int kPowLo = 64, kPowHi = 24;     // K^i (i < 64) and K^(64 i) (i < 24: exponents below 1536)
 constexpr int kPowInv = 4;                   // K^-z (z < 4)
 
-// ablation switches (tools/ablate_route.hip); the product instantiates ABL_NONE
+// ---------------------------------------------------------------------------------------
+// The kernels' variant mask (template <unsigned ABL>): three groups of flags in one word. A flag's
+// value is part of the kernels' symbol names (and of the names in saved profiles), so values never
+// change and a retired flag's bit is not reused.
+// ---------------------------------------------------------------------------------------
+// Product variants of route_kernel and route_chunk_kernel (same records, bit for bit; route_host.hpp
+// picks per launch).
+enum : unsigned {
+    KV_UNIFORM = 0,         // lane layout: every line of a tile on the same G lanes
+    KV_SEGMENTS = 1u << 22, // lane layout: a tile of mixed line lengths, one lane per 64-byte name segment
+    KV_CHUNKS = 1u << 23,   // lane layout: the chunk-layout kernel (route_chunk_kernel, chunk_kernel.hpp)
+    // KV_ALIVE: a launch whose every shard is alive (the shard is h % N): no probe, overlay, deferral or
+    // probed-dead marks in the kernel, and none of their registers.
+    KV_ALIVE = 1u << 28,
+    // KV_PICKS: a launch with dead shards whose probes end after the first picks (one dead shard: two
+    // picks always find a live one; two or more: the deferral of probe_defer_kernel) runs a variant
+    // with chunk_probe in place of probe_shard, whose 16-entry overlay loop it cannot reach.
+    KV_PICKS = 1u << 29,
+    // KV_DEFER1: the common dead-shard launch, two or more of at most 64 shards dead with every probe that
+    // meets a dead shard deferred after one pick (probe_defer_kernel redoes it whole and notes the dead
+    // shards it visits): the probe is h % N and one test of the alive word (a kernel argument), with no
+    // reciprocal or alive pads in LDS, no marks and no pending list (a variant of the picks-only and
+    // chunk kernels).
+    KV_DEFER1 = 1u << 31,
+    // KV_DEAD1: exactly one dead shard (RouteParams::dead_k): find_downstream's two picks in closed form,
+    // the second pick's reciprocal a kernel argument (magic_n1), no alive or reciprocal pads in LDS.
+    KV_DEAD1 = 1u << 27,
+    // KV_HIST1: the KV_DEAD1 uniform / segment variant that also counts the tile histograms of a route + pack
+    // launch (RouteParams::hist); a variant of its own because the counting costs the route-only variant
+    // 3 % in SGPR spills (every-shard-alive variants count them at no cost)
+    KV_HIST1 = 1u << 20,
+};
+// Developer switches of route_kernel, never in the shipped library: parts switched off for the `alive` and
+// `quick` tables of tools/ablate_route.hip and the SR_VARIANT dispatch of `make VARIANTS=1` builds
+// (records wrong or missing by design in most), and the diagnostic stamps of tools/stamps_route.hip.
 enum : unsigned {
     ABL_NONE = 0,
-    ABL_NO_LOOKBACK = 1u,   // base = 0 (records overwrite each other)
-    ABL_NO_LINES = 2u,      // skip per-line staging / hashing / records
-    ABL_NO_PROLOGUE = 4u,   // skip the straddling-line prologue
-    ABL_NO_SCAN = 8u,       // skip masks/Horner/scans (counts only)
-    ABL_LOAD_ONLY = 16u,    // load the tile into LDS and count '\n' only
-    ABL_STAMPS = 32u,       // diagnostic: s_memrealtime at phase boundaries into RouteParams::dbg
-    ABL_NO_XCD_LOCAL = 64u, // deal every launch's tiles round-robin even when it has 8+ batches
-    ABL_NO_HASH = 256u,     // ablation: skip the sdbm (h = 0); staging, probe and records stay
-    ABL_LDS_PAD = 131072u,  // occupancy experiment: 4 KiB of unused LDS per workgroup
-    ABL_OLD_MASKS = 65536u,  // round-1 v0.5 piece masks (one SWAR test per pattern)
-    ABL_OLD_SCANNER = 32768u, // round-1 v0.5 scanner: one wave polls and publishes
-    ABL_FAKE_BASE = 4096u,  // ablation: base = t * (this tile's count), exact only for uniform tiles (C2)
-    ABL_EARLY_BASE = 2048u,  // also read the record base when staging ends (round-1 v0.6a/b; no gain once
-                             // the pipelined scanner publishes ahead of need)
-    ABL_AGENT_GRANULES = 262144u,  // every count / base granule stored sc1 (round-1 v0.5), whatever the XCDs
-    ABL_SCAN_SERIAL = 524288u,  // round-1 v0.6 scanner: 256 granules per round trip, one poll in flight
-    ABL_NO_MID_BASE = 2097152u,  // no base read part-way through the hash (round-1 v0.8)
-    ABL_OLD_HASH = 1024u,   // round-1 v0.5 per-segment sdbm (v_alignbyte reads, compiler-extracted bytes)
+    ABL_NO_LOOKBACK = 1u << 0,   // base = 0 (records overwrite each other)
+    ABL_NO_LINES = 1u << 1,      // skip per-line staging / hashing / records
+    ABL_NO_PROLOGUE = 1u << 2,   // skip the straddling-line prologue
+    ABL_LOAD_ONLY = 1u << 4,     // load the tile into LDS and count '\n' only
+    ABL_STAMPS = 1u << 5,        // diagnostic: s_memrealtime at phase boundaries into RouteParams::dbg
+    ABL_NO_HASH = 1u << 8,       // skip the sdbm (h = 0); staging, probe and records stay
+    ABL_FAKE_BASE = 1u << 12,    // base = t * (this tile's count), exact only for uniform tiles (C2)
+    ABL_NO_MID_BASE = 1u << 21,  // no base read part-way through the hash (round-1 v0.8)
 };
+// Developer ablations of route_chunk_kernel (timing / counter attribution only, wrong records; built
+// with -DSR_CHUNK_ABL=<mask> into tools/ab, never shipped)
+enum : unsigned { CH_ABL_NO_U = 1u << 24, CH_ABL_NO_SUF = 1u << 25, CH_ABL_NO_EMIT = 1u << 26 };
 
-// Product kernel variants (same records, bit for bit): KV_SEGMENTS lays a tile of mixed line
-// lengths out one lane per 64-byte name segment (route_host.hpp picks the variant per launch).
-// KV_ALIVE: a launch whose every shard is alive (the shard is h % N): no probe, overlay, deferral or
-// probed-dead marks in the kernel, and none of their registers.
-// KV_PICKS: a launch with dead shards whose probes end after the first picks (one dead shard: two
-// picks always find a live one; two or more: the deferral of probe_defer_kernel) runs a variant
-// with chunk_probe in place of probe_shard, whose 16-entry overlay loop it cannot reach.
-enum : unsigned { KV_UNIFORM = 0u, KV_SEGMENTS = 4194304u, KV_ALIVE = 268435456u, KV_PICKS = 536870912u };
-// KV_DEFER1: the common dead-shard launch, two or more of at most 64 shards dead with every probe that
-// meets a dead shard deferred after one pick (probe_defer_kernel redoes it whole and notes the dead
-// shards it visits): the probe is h % N and one test of the alive word (a kernel argument), with no
-// reciprocal or alive pads in LDS, no marks and no pending list (a variant of the picks-only and
-// chunk kernels).
-constexpr unsigned KV_DEFER1 = 2147483648u;
-// KV_DEAD1: exactly one dead shard (RouteParams::dead_k): find_downstream's two picks in closed form,
-// the second pick's reciprocal a kernel argument (magic_n1), no alive or reciprocal pads in LDS.
-constexpr unsigned KV_DEAD1 = 134217728u;
-// KV_HIST1: the KV_DEAD1 uniform / segment variant that also counts the tile histograms of a route + pack
-// launch (RouteParams::hist); a variant of its own because the counting costs the route-only variant
-// 3 % in SGPR spills (every-shard-alive variants count them at no cost)
-constexpr unsigned KV_HIST1 = 1048576u;
+constexpr unsigned kKvBits = KV_SEGMENTS | KV_CHUNKS | KV_ALIVE | KV_PICKS | KV_DEFER1 | KV_DEAD1 | KV_HIST1;
+constexpr unsigned kAblBits = ABL_NO_LOOKBACK | ABL_NO_LINES | ABL_NO_PROLOGUE | ABL_LOAD_ONLY | ABL_STAMPS |
+                              ABL_NO_HASH | ABL_FAKE_BASE | ABL_NO_MID_BASE;
+constexpr unsigned kChAblBits = CH_ABL_NO_U | CH_ABL_NO_SUF | CH_ABL_NO_EMIT;
+static_assert((kKvBits & kAblBits) == 0 && (kKvBits & kChAblBits) == 0 && (kAblBits & kChAblBits) == 0,
+              "the three groups of variant flags are disjoint");
+static_assert(__builtin_popcount(kKvBits) == 7 && __builtin_popcount(kAblBits) == 8 && __builtin_popcount(kChAblBits) == 3,
+              "no two variant flags share a bit (one bit per flag listed above)");
+
 template <unsigned ABL>
 constexpr bool kCountsHist = (ABL & KV_ALIVE) != 0 || ((ABL & KV_DEAD1) != 0 && (ABL & KV_HIST1) != 0);
 
@@ -250,19 +280,6 @@ __device__ __forceinline__ uint64_t sdbm_step(uint64_t h, uint32_t byte) {
     return (h << 16) + (h << 6) - h + (uint64_t)c;
 }
 
-// Four Horner steps at once (bytes in memory order = little-endian byte order of x):
-//   h*K^4 + (c0*K + c1)*K^2 + (c2*K + c3),   K^2 = 2^32 + 0x7E0F81.
-// The pair terms are exact 32-bit multiply-adds; only the final step needs 64-bit multiplies,
-// so the dword costs one 64x64 product instead of four (the 64-bit multiplies are the slow ops).
-__device__ __forceinline__ uint64_t sdbm_dword(uint64_t h, uint32_t x) {
-    const int32_t c0 = (int8_t)(x & 0xFFu), c1 = (int8_t)((x >> 8) & 0xFFu);
-    const int32_t c2 = (int8_t)((x >> 16) & 0xFFu), c3 = (int8_t)(x >> 24);
-    const int32_t t = c0 * (int32_t)K + c1;
-    const int32_t u = c2 * (int32_t)K + c3;
-    const uint64_t d = (uint64_t)((int64_t)t * kK2lo) + (uint64_t)(int64_t)u + ((uint64_t)(uint32_t)t << 32);
-    return h * kK4 + d;
-}
-
 // Signed-byte pair products by SDWA (byte select + sign extension folded into the VALU op):
 // c0 * K + c1 and c2 * K + c3 for the bytes c0..c3 of x, two instructions each.
 __device__ __forceinline__ int32_t pair_lo(uint32_t x) {
@@ -282,7 +299,11 @@ __device__ __forceinline__ int32_t pair_hi(uint32_t x) {
     return t;
 }
 
-// sdbm_dword with the pair products from SDWA: 11 VALU per dword.
+// Four Horner steps at once (bytes in memory order = little-endian byte order of x):
+//   h*K^4 + (c0*K + c1)*K^2 + (c2*K + c3),   K^2 = 2^32 + 0x7E0F81.
+// The pair terms (from SDWA) are exact 32-bit multiply-adds; only the final step needs 64-bit
+// multiplies, so the dword costs one 64x64 product instead of four (the 64-bit multiplies are the
+// slow ops): 11 VALU per dword.
 __device__ __forceinline__ uint64_t sdbm_dword_fast(uint64_t h, uint32_t x) {
     const int32_t t = pair_lo(x);
     const int32_t u = pair_hi(x);
@@ -319,22 +340,6 @@ __device__ __forceinline__ uint64_t sdbm_qword_fast(uint64_t h, uint32_t x0, uin
     return ((uint64_t)hi << 32) | (uint32_t)acc;
 }
 
-// keep the bytes of dword x whose index within it is >= lo and < hi (0..4)
-__device__ __forceinline__ uint32_t byte_range(uint32_t x, int lo, int hi) {
-    const uint32_t mlo = lo <= 0 ? 0xFFFFFFFFu : (lo >= 4 ? 0u : ~((1u << (8 * lo)) - 1u));
-    const uint32_t mhi = hi >= 4 ? 0xFFFFFFFFu : (hi <= 0 ? 0u : ((1u << (8 * hi)) - 1u));
-    return x & mlo & mhi;
-}
-
-// Horner of the bytes of a 16-byte piece whose piece index is in [lo, hi), others zeroed.
-__device__ __forceinline__ uint64_t sdbm_piece(uint4 v, int lo, int hi) {
-    uint64_t h = 0;
-    h = sdbm_dword(h, byte_range(v.x, lo, hi));
-    h = sdbm_dword(h, byte_range(v.y, lo - 4, hi - 4));
-    h = sdbm_dword(h, byte_range(v.z, lo - 8, hi - 8));
-    return sdbm_dword(h, byte_range(v.w, lo - 12, hi - 12));
-}
-
 // 4-bit mask of the bytes of x equal to the byte replicated in pat (exact SWAR test).
 __device__ __forceinline__ uint32_t eq_mask4(uint32_t x, uint32_t pat) {
     const uint32_t t = x ^ pat;
@@ -347,23 +352,8 @@ __device__ __forceinline__ uint32_t eq_mask16(uint4 v, uint32_t pat) {
            (eq_mask4(v.w, pat) << 12);
 }
 
-// 0x80 in every byte of x equal to the byte replicated in pat, 0 elsewhere (exact, 5 VALU ops)
-__device__ __forceinline__ uint32_t eq_flags(uint32_t x, uint32_t pat) {
-    const uint32_t t = x ^ pat;
-    return ~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t) & 0x80808080u;
-}
-
-// 16-bit mask (bit i = byte i) of the bytes of a 16-byte piece equal to pat. The 0x80 flags of
-// two dwords are packed by two v_dot4_u32_u8 with byte weights 1..128 (= 128 x the 8-bit mask).
-__device__ __forceinline__ uint32_t eq_mask16_dot(uint4 v, uint32_t pat) {
-    uint32_t lo = __builtin_amdgcn_udot4(eq_flags(v.x, pat), 0x08040201u, 0u, false);
-    lo = __builtin_amdgcn_udot4(eq_flags(v.y, pat), 0x80402010u, lo, false);
-    uint32_t hi = __builtin_amdgcn_udot4(eq_flags(v.z, pat), 0x08040201u, 0u, false);
-    hi = __builtin_amdgcn_udot4(eq_flags(v.w, pat), 0x80402010u, hi, false);
-    return (lo + (hi << 8)) >> 7;
-}
-
-// '\n' and ':' masks (bit i = byte i) of a 16-byte piece, 7 VALU per dword for both patterns.
+// '\n' and ':' masks (bit i = byte i) of a 16-byte piece, 7 VALU per dword for both patterns: the
+// 0x80 flags of two dwords are packed by two v_dot4_u32_u8 with byte weights 1..128 (= 128 x the mask).
 // For a pattern P with bit 7 clear, byte b == P iff bit 7 of b is clear and ((b & 0x7F) ^ P) + 0x7F
 // has bit 7 clear (the sum stays within the byte): the masked bytes and ~b's bit 7 are shared by
 // both patterns, the xor-add is one v_xad_u32, and the flag one v_bfi_b32.
@@ -444,12 +434,6 @@ __device__ __forceinline__ uint32_t mod_magic(uint64_t n, const Magic &mg, uint3
     return (uint32_t)(n - div_magic(n, mg) * (uint64_t)d);
 }
 
-__device__ __forceinline__ uint64_t shfl_up64(uint64_t v, int d) {
-    const uint32_t lo = __shfl_up((uint32_t)v, d, 64);
-    const uint32_t hi = __shfl_up((uint32_t)(v >> 32), d, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
 __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int d) {
     const uint32_t lo = __shfl_xor((uint32_t)v, d, 64);
     const uint32_t hi = __shfl_xor((uint32_t)(v >> 32), d, 64);
@@ -459,12 +443,6 @@ __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int d) {
 __device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += shfl_xor64(v, d);
-    return v;
-}
-
-__device__ __forceinline__ int wave_max_i32(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
     return v;
 }
 
@@ -550,22 +528,6 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t v, int lane) {
 template <unsigned ABL>
 __device__ __forceinline__ void stamp(const RouteParams &p, int tid, uint32_t t, int slot) {
     if ((ABL & ABL_STAMPS) && tid == 0) p.dbg[(size_t)t * 16 + slot] = __builtin_amdgcn_s_memrealtime();
-}
-
-// Segmented "line state" scan element: [63:32] newline count, [31] lane range holds a '\n',
-// [16:0] first ':' of the line open at the right end of the range (tile position, kNone = none).
-// combine(f, g) for f left of g: counts add; if g holds a '\n' its state wins, else the open
-// line continues from f and its first colon is the earlier one.
-__device__ __forceinline__ uint64_t seg_combine(uint64_t f, uint64_t g) {
-    const uint64_t cnt = (f & 0xFFFFFFFF00000000ull) + (g & 0xFFFFFFFF00000000ull);
-    uint32_t lo;
-    if ((uint32_t)g & 0x80000000u) {
-        lo = (uint32_t)g;
-    } else {
-        const uint32_t fc = (uint32_t)f & 0x1FFFFu, gc = (uint32_t)g & 0x1FFFFu;
-        lo = ((uint32_t)f & 0x80000000u) | (fc < gc ? fc : gc);
-    }
-    return cnt | lo;
 }
 
 __device__ __forceinline__ uint64_t mk_status(uint32_t epoch, uint32_t flag, uint32_t value) {
@@ -801,16 +763,16 @@ __device__ __forceinline__ void mark_tile_end(const RouteParams &p, const uint32
 // a 256-thread workgroup is admitted min(8, floor(800 / (ceil(sgpr / 16) * 16 + 16))) times per CU,
 // which is 7 from 81 SGPRs on, whatever the occupancy query and the compiler's remark say.
 // (ABL_STAMPS, the diagnostic build of tools/stamps_route.hip, keeps the shape of what it stamps.)
-template <int BLOCK, unsigned ABL>
-constexpr bool kOcc8 = BLOCK == 256 && (ABL & ~ABL_STAMPS) == (KV_UNIFORM | KV_ALIVE);
+template <unsigned ABL>
+constexpr bool kOcc8 = (ABL & ~ABL_STAMPS) == (KV_UNIFORM | KV_ALIVE);
 
-template <int BLOCK, bool SLIM = false>
+template <bool SLIM = false>
 struct SmemT {
     typedef int32_t pos_t;
-    static constexpr int kWaves = BLOCK / 64;
-    static constexpr int kTileB = BLOCK * kLaneBytes;
+    static constexpr int kWaves = kBlock / 64;
+    static constexpr int kTileB = kTile;
     static constexpr int kHalo = 2048;                // bytes before the tile kept in LDS
-    static constexpr int kWin = BLOCK;                // tile-local lines staged per round
+    static constexpr int kWin = kBlock;               // tile-local lines staged per round
     // LDS image of the batch bytes [T0 - kHalo, T0 + tile): 64-byte rows stored as 17 dwords (one
     // pad dword per row) so that lanes reading at 64-byte strides hit distinct banks.
     static constexpr int kRows = (kHalo + kTileB) / 64;
@@ -852,13 +814,13 @@ struct SmemT {
 //    (entry i: low word in row 2 i, high word in row 2 i + 1), which only the probes of the
 //    dead-shard variants use otherwise; they are read for names of more than 64 bytes only. K^r
 //    (r < 4), read once per line, stays an array of its own.
-template <int BLOCK>
-struct SmemT<BLOCK, true> {
+template <>
+struct SmemT<true> {
     typedef uint16_t pos_t;
-    static constexpr int kWaves = BLOCK / 64;
-    static constexpr int kTileB = BLOCK * kLaneBytes;
+    static constexpr int kWaves = kBlock / 64;
+    static constexpr int kTileB = kTile;
     static constexpr int kHalo = 1536;
-    static constexpr int kWin = BLOCK;
+    static constexpr int kWin = kBlock;
     static constexpr int kRows = (kHalo + kTileB) / 64;
     static constexpr int kWords = kRows * 17 + 20;
     static constexpr int kPowWords = (kPowLo + kPowHi) * 2;
@@ -885,53 +847,19 @@ struct SmemT<BLOCK, true> {
     }
     __device__ __forceinline__ uint64_t pow_hi(int i) const { return pow_lo(kPowLo + i); }
 };
-static_assert(sizeof(SmemT<256, true>) <= 20480, "eight workgroups per CU: 160 KiB of LDS");
-
-// K^-z for z = 1, 2, 3 (undoing z bytes of zero padding)
-__device__ __forceinline__ uint64_t kinv_small(int z) {
-    constexpr uint64_t i1 = kKinv, i2 = kKinv * kKinv, i3 = kKinv * kKinv * kKinv;
-    return z == 1 ? i1 : (z == 2 ? i2 : i3);
-}
+static_assert(sizeof(SmemT<true>) <= 20480, "eight workgroups per CU: 160 KiB of LDS");
 
 // K^n for 0 <= n < 1536 from the LDS tables
 template <class S>
 __device__ __forceinline__ uint64_t kpow_n(const S &sm, int n) {
     return sm.kp_hi[n >> 6] * sm.kp_lo[n & 63];
 }
-template <int BLOCK>
-__device__ __forceinline__ uint64_t kpow_n(const SmemT<BLOCK, true> &sm, int n) {
+__device__ __forceinline__ uint64_t kpow_n(const SmemT<true> &sm, int n) {
     return sm.pow_hi(n >> 6) * sm.pow_lo(n & 63);
 }
 
 // dword index in the padded LDS image of image byte b (b % 4 == 0 for whole dwords)
 __device__ __forceinline__ int img_dw(int b) { return (b >> 6) * 17 + ((b >> 2) & 15); }
-
-// sdbm (Horner, no colon test) of the n <= 64 image bytes starting at image byte a.
-// Aligned dword reads + v_alignbyte; whole dwords by sdbm_dword, the tail through the
-// zero-padding identity Horner(x, 0^z) = Horner(x) * K^z.
-template <class S>
-__device__ __forceinline__ uint64_t sdbm_lds(const S &sm, int a, int n) {
-    const int base = a & ~3, sh = a & 3;
-    const int i0 = img_dw(base), r0 = base & 63;
-    const int nfull = n >> 2, rem = n & 3;
-    uint32_t w[17];
-#pragma unroll
-    for (int m = 0; m < 17; ++m) w[m] = sm.img[i0 + m + ((r0 + 4 * m) >> 6)];
-    uint64_t h = 0;
-#pragma unroll
-    for (int m = 0; m < 16; ++m) {
-        if (m < nfull) h = sdbm_dword(h, __builtin_amdgcn_alignbyte(w[m + 1], w[m], sh));
-    }
-    if (rem) {
-        uint32_t x = 0;
-#pragma unroll
-        for (int m = 0; m < 16; ++m)
-            if (m == nfull) x = __builtin_amdgcn_alignbyte(w[m + 1], w[m], sh);
-        x &= (1u << (8 * rem)) - 1u;
-        h = sdbm_dword(h, x) * kinv_small(4 - rem);
-    }
-    return h;
-}
 
 // sdbm of the 0 < n <= 64 image bytes starting at image byte a, from aligned dword reads: the
 // bytes of the first dword before a are zeroed (leading zeros leave a Horner value unchanged), the
@@ -994,9 +922,8 @@ __device__ __forceinline__ uint4 img_get16(const S &sm, int b) {
 
 // Number of '\n' bytes in tile m, counted by one wave (only used when a predecessor has not
 // published its count within the spin budget).
-template <int BLOCK>
 __device__ uint32_t count_tile_wave(uint32_t nbytes, __amdgpu_buffer_rsrc_t rsrc, uint32_t m, int lane) {
-    constexpr uint32_t T = BLOCK * kLaneBytes;
+    constexpr uint32_t T = kTile;
     uint32_t c = 0;
     for (uint32_t off = lane * 16; off < T; off += 1024) {
         const uint4 v = load16(rsrc, m * T + off, nbytes);
@@ -1040,76 +967,7 @@ __device__ __forceinline__ bool granule_ok(uint64_t st, uint32_t ep, uint32_t fl
     return (uint32_t)(st >> 34) == ep && ((st >> 32) & 3u) == flag;
 }
 
-template <int BLOCK>
-__device__ void scan_batch(const RouteParams &p, const BatchDesc &bd, uint32_t epoch, int lane) {
-    constexpr int kGroups = 4;   // 64-tile groups polled per round
-    const uint64_t *status = p.status + bd.sbase;
-    uint64_t *bases = p.bases + bd.sbase;
-    const __amdgpu_buffer_rsrc_t rsrc =
-        __builtin_amdgcn_make_buffer_rsrc((void *)bd.bytes, (short)0, (int)bd.nbytes, 0x00020000);
-    const uint32_t ep = epoch & 0x3FFFFFFFu;
-    uint32_t run = 0;
-    uint32_t c = 0;      // first tile whose base is not yet published
-    int spin = 0;        // rounds without progress on group c
-    while (c < bd.ntiles) {
-        // one round trip: the counts of up to kGroups groups from c on
-        uint32_t cnt[kGroups];
-        bool have[kGroups];
-#pragma unroll
-        for (int k = 0; k < kGroups; ++k) {
-            const uint32_t tt = c + 64 * k + lane;
-            cnt[k] = 0;
-            have[k] = tt >= bd.ntiles;
-            if (!have[k]) {
-                const uint64_t st = __hip_atomic_load(&status[tt], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (granule_ok(st, ep, kFlagAgg)) {
-                    cnt[k] = (uint32_t)st & kCountMask;
-                    have[k] = true;
-                }
-            }
-        }
-        // head group still incomplete after the spin budget: count its silent tiles here
-        if (spin >= kSpinBudget) {
-            uint64_t missing = __ballot(!have[0]);
-            while (missing) {
-                const int L = __builtin_ctzll(missing);
-                missing &= missing - 1;
-                const uint32_t c2 = count_tile_wave<BLOCK>(bd.nbytes, rsrc, c + (uint32_t)L, lane);
-                if (lane == L) {
-                    cnt[0] = c2;
-                    have[0] = true;
-                }
-            }
-        }
-        // publish the longest complete prefix (tile by tile, so a tile never waits for a later one)
-        bool progress = false;
-#pragma unroll
-        for (int k = 0; k < kGroups; ++k) {
-            const uint64_t missing = __ballot(!have[k]);
-            const int nready = missing ? __builtin_ctzll(missing) : 64;
-            if (nready == 0) break;
-            const uint32_t tt = c + lane;   // c has advanced by 64 per fully published group
-            const uint32_t v = lane < nready ? cnt[k] : 0u;
-            const uint32_t incl = wave_incl_add32(v);
-            if (lane < nready && tt < bd.ntiles)
-                __hip_atomic_store(&bases[tt], mk_status(epoch, kFlagBase, run + incl - v), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-            run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-            c += (uint32_t)nready;
-            progress = true;
-            if (nready < 64 || c >= bd.ntiles) break;
-        }
-        if (progress) {
-            spin = 0;
-        } else {
-            ++spin;
-            __builtin_amdgcn_s_sleep(1);
-        }
-    }
-    if (lane == 0) *bd.n_out = run;
-}
-
-// Scanner with its global stores split off (the product's): on gfx9 a wave's stores share vmcnt
+// The scanner, with its global stores split off: on gfx9 a wave's stores share vmcnt
 // with its loads, so a scanner that also published would wait for its own stores before every
 // poll. Wave 0 polls the tiles' counts and computes their bases into an LDS ring (head index
 // released after the writes); wave 1 publishes the ring to the bases granules and the batch's
@@ -1119,161 +977,79 @@ __device__ __forceinline__ uint32_t stamp_block(const RouteParams &p, const Batc
     return p.xcd_local ? (bd.tile0 + t) * 8u + bd.cls : bd.tile0 + t;
 }
 
-template <int BLOCK, unsigned ABL, class S>
+template <unsigned ABL, class S>
 __device__ void scan_batch_split(const RouteParams &p, const BatchDesc &bd, uint32_t epoch, S &sm,
                                  int wave, int lane) {
     constexpr uint32_t kRing = 4096;
     static_assert(S::kWords >= (int)kRing, "scanner ring in the LDS image");
     uint32_t *const ring = sm.img;
     if (wave == 0) {
-        constexpr int kGroups = 4;
         const uint64_t *status = p.status + bd.sbase;
         const __amdgpu_buffer_rsrc_t rsrc =
             __builtin_amdgcn_make_buffer_rsrc((void *)bd.bytes, (short)0, (int)bd.nbytes, 0x00020000);
         const uint32_t ep = epoch & 0x3FFFFFFFu;
         // tiles that share this XCD get their base by a plain store (ring entry bit 31)
-        constexpr bool kAgentOnly = (ABL & ABL_AGENT_GRANULES) != 0;
-        const uint32_t mine = kAgentOnly ? 0u : (8u | xcc_id()) << 28;
-        if (lane == 0 && !kAgentOnly)
+        const uint32_t mine = (8u | xcc_id()) << 28;
+        if (lane == 0)
             __hip_atomic_store(&p.ctl->scan_xcc[blockIdx.x], mk_status(epoch, kFlagXcc, xcc_id()), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
-        uint32_t run = 0, c = 0, rounds = 0;
+        uint32_t run = 0, c = 0;
         int spin = 0;
-        if (!(ABL & ABL_SCAN_SERIAL)) {
-            // Pipelined polls of the 64 granules from c: the next poll is issued before the previous
-            // one is consumed, so two are in flight and the scanner looks every half round trip
-            // (a poll's round trip under the tiles' load is ~1.2 us). Unrolled by two with the
-            // roles of the two poll registers swapped, so no copy waits for a poll in flight.
-            const uint32_t last = bd.ntiles - 1u;
-            auto poll = [&](uint32_t c0) -> uint64_t {   // unconditional load: clamped address
-                const uint32_t tt = c0 + lane < last ? c0 + lane : last;
-                return __hip_atomic_load(&status[tt], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            };
-            // consume poll `cur` (tiles [ccur, ccur + 64)) from c, with poll `nxt` issued first
-            auto step = [&](uint64_t cur, uint32_t ccur, uint64_t &nxt, uint32_t &cnxt) {
-                while (c + 64 > __hip_atomic_load(&sm.scan_pub, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) + kRing)
-                    __builtin_amdgcn_s_sleep(1);
-                cnxt = c;
-                nxt = poll(c);
-                const int sh = (int)(c - ccur);
-                uint64_t st = cur;
-                if (sh) {
-                    const int src = (lane + sh) & 63;
-                    st = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(cur >> 32), src) << 32) |
-                         (uint32_t)__shfl((int)(uint32_t)cur, src);
-                }
-                const uint32_t tt = c + lane;
-                uint32_t cnt = 0, loc = 0;
-                bool have = tt >= bd.ntiles;
-                if (!have && lane + sh < 64 && granule_ok(st, ep, kFlagAgg)) {
-                    cnt = (uint32_t)st & kCountMask;
-                    loc = ((uint32_t)st & ~kCountMask) == mine && mine ? 0x80000000u : 0u;
-                    have = true;
-                }
-                if (spin >= kSpinBudget) {   // still incomplete: count the silent tiles here
-                    uint64_t missing = __ballot(!have);
-                    while (missing) {
-                        const int L = __builtin_ctzll(missing);
-                        missing &= missing - 1;
-                        const uint32_t c2 = count_tile_wave<BLOCK>(bd.nbytes, rsrc, c + (uint32_t)L, lane);
-                        if (lane == L) {
-                            cnt = c2;
-                            have = true;
-                        }
-                    }
-                }
-                const uint64_t missing = __ballot(!have);
-                const int nready = missing ? __builtin_ctzll(missing) : 64;
-                if (nready) {
-                    const uint32_t v = lane < nready ? cnt : 0u;
-                    const uint32_t incl = wave_incl_add32(v);
-                    if (lane < nready && tt < bd.ntiles) {
-                        ring[tt % kRing] = (run + incl - v) | loc;
-                        if (ABL & ABL_STAMPS)
-                            p.dbg[(size_t)stamp_block(p, bd, tt) * 16 + 13] = __builtin_amdgcn_s_memrealtime();
-                    }
-                    run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-                    c += (uint32_t)nready;
-                    if (c > bd.ntiles) c = bd.ntiles;
-                    spin = 0;
-                    if (lane == 0) {
-                        if (c >= bd.ntiles) sm.scan_total = run;
-                        __hip_atomic_store(&sm.scan_head, c, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
-                } else {
-                    ++spin;
-                    __builtin_amdgcn_s_sleep(1);
-                }
-            };
-            uint64_t pa = poll(0), pb = 0;
-            uint32_t ca = 0, cb = 0;
-            while (c < bd.ntiles) {
-                step(pa, ca, pb, cb);
-                if (c >= bd.ntiles) break;
-                step(pb, cb, pa, ca);
-            }
-        }
-        while (c < bd.ntiles) {
-            // the publisher must have taken the ring slots this round may overwrite
-            while (c + 64 * kGroups > __hip_atomic_load(&sm.scan_pub, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) +
-                                          kRing)
+        // Pipelined polls of the 64 granules from c: the next poll is issued before the previous
+        // one is consumed, so two are in flight and the scanner looks every half round trip
+        // (a poll's round trip under the tiles' load is ~1.2 us). Unrolled by two with the
+        // roles of the two poll registers swapped, so no copy waits for a poll in flight.
+        const uint32_t last = bd.ntiles - 1u;
+        auto poll = [&](uint32_t c0) -> uint64_t {   // unconditional load: clamped address
+            const uint32_t tt = c0 + lane < last ? c0 + lane : last;
+            return __hip_atomic_load(&status[tt], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        };
+        // consume poll `cur` (tiles [ccur, ccur + 64)) from c, with poll `nxt` issued first
+        auto step = [&](uint64_t cur, uint32_t ccur, uint64_t &nxt, uint32_t &cnxt) {
+            while (c + 64 > __hip_atomic_load(&sm.scan_pub, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) + kRing)
                 __builtin_amdgcn_s_sleep(1);
-            uint32_t cnt[kGroups], loc[kGroups];
-            bool have[kGroups];
-            const uint64_t t_iss = (ABL & ABL_STAMPS) ? __builtin_amdgcn_s_memrealtime() : 0;
-#pragma unroll
-            for (int k = 0; k < kGroups; ++k) {
-                const uint32_t tt = c + 64 * k + lane;
-                cnt[k] = 0;
-                loc[k] = 0;
-                have[k] = tt >= bd.ntiles;
-                if (!have[k]) {
-                    const uint64_t st = __hip_atomic_load(&status[tt], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (granule_ok(st, ep, kFlagAgg)) {
-                        cnt[k] = (uint32_t)st & kCountMask;
-                        loc[k] = ((uint32_t)st & ~kCountMask) == mine && mine ? 0x80000000u : 0u;
-                        have[k] = true;
-                    }
-                }
+            cnxt = c;
+            nxt = poll(c);
+            const int sh = (int)(c - ccur);
+            uint64_t st = cur;
+            if (sh) {
+                const int src = (lane + sh) & 63;
+                st = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(cur >> 32), src) << 32) |
+                     (uint32_t)__shfl((int)(uint32_t)cur, src);
             }
-            if (ABL & ABL_STAMPS) {   // poll round trips: (issue, all returned) per round
-                if (lane == 0) {
-                    const size_t o = 300000u + blockIdx.x * 4096u + (rounds & 2047u) * 2u;
-                    p.dbg[o] = t_iss;
-                    p.dbg[o + 1] = __builtin_amdgcn_s_memrealtime();
-                }
-                ++rounds;
+            const uint32_t tt = c + lane;
+            uint32_t cnt = 0, loc = 0;
+            bool have = tt >= bd.ntiles;
+            if (!have && lane + sh < 64 && granule_ok(st, ep, kFlagAgg)) {
+                cnt = (uint32_t)st & kCountMask;
+                loc = ((uint32_t)st & ~kCountMask) == mine && mine ? 0x80000000u : 0u;
+                have = true;
             }
-            if (spin >= kSpinBudget) {   // head group still incomplete: count its silent tiles here
-                uint64_t missing = __ballot(!have[0]);
+            if (spin >= kSpinBudget) {   // still incomplete: count the silent tiles here
+                uint64_t missing = __ballot(!have);
                 while (missing) {
                     const int L = __builtin_ctzll(missing);
                     missing &= missing - 1;
-                    const uint32_t c2 = count_tile_wave<BLOCK>(bd.nbytes, rsrc, c + (uint32_t)L, lane);
+                    const uint32_t c2 = count_tile_wave(bd.nbytes, rsrc, c + (uint32_t)L, lane);
                     if (lane == L) {
-                        cnt[0] = c2;
-                        have[0] = true;
+                        cnt = c2;
+                        have = true;
                     }
                 }
             }
-            const uint32_t c_start = c;
-#pragma unroll
-            for (int k = 0; k < kGroups; ++k) {
-                const uint64_t missing = __ballot(!have[k]);
-                const int nready = missing ? __builtin_ctzll(missing) : 64;
-                if (nready == 0) break;
-                const uint32_t v = lane < nready ? cnt[k] : 0u;
+            const uint64_t missing = __ballot(!have);
+            const int nready = missing ? __builtin_ctzll(missing) : 64;
+            if (nready) {
+                const uint32_t v = lane < nready ? cnt : 0u;
                 const uint32_t incl = wave_incl_add32(v);
-                if (lane < nready && c + lane < bd.ntiles) {
-                    ring[(c + lane) % kRing] = (run + incl - v) | loc[k];
-                    if (ABL & ABL_STAMPS) p.dbg[(size_t)stamp_block(p, bd, c + lane) * 16 + 13] = __builtin_amdgcn_s_memrealtime();
+                if (lane < nready && tt < bd.ntiles) {
+                    ring[tt % kRing] = (run + incl - v) | loc;
+                    if (ABL & ABL_STAMPS)
+                        p.dbg[(size_t)stamp_block(p, bd, tt) * 16 + 13] = __builtin_amdgcn_s_memrealtime();
                 }
                 run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
                 c += (uint32_t)nready;
-                if (nready < 64 || c >= bd.ntiles) break;
-            }
-            if (c > bd.ntiles) c = bd.ntiles;
-            if (c != c_start) {
+                if (c > bd.ntiles) c = bd.ntiles;
                 spin = 0;
                 if (lane == 0) {
                     if (c >= bd.ntiles) sm.scan_total = run;
@@ -1283,6 +1059,13 @@ __device__ void scan_batch_split(const RouteParams &p, const BatchDesc &bd, uint
                 ++spin;
                 __builtin_amdgcn_s_sleep(1);
             }
+        };
+        uint64_t pa = poll(0), pb = 0;
+        uint32_t ca = 0, cb = 0;
+        while (c < bd.ntiles) {
+            step(pa, ca, pb, cb);
+            if (c >= bd.ntiles) break;
+            step(pb, cb, pa, ca);
         }
     } else if (wave == 1) {
         uint64_t *const bases = p.bases + bd.sbase;
@@ -1371,12 +1154,11 @@ __device__ void arrive(const RouteParams &p, uint32_t blk, uint32_t epoch) {
 template <unsigned ABL>
 constexpr bool kEarlyArrive = (ABL & KV_SEGMENTS) == 0 && (ABL & (KV_ALIVE | KV_PICKS | KV_DEFER1 | KV_DEAD1)) != 0;
 
-template <int BLOCK, unsigned ABL>
+template <unsigned ABL>
 struct KernelTraits {
-    // waves per SIMD to reserve registers for: 1024-thread tiles run one workgroup per CU,
-    // smaller tiles several (LDS: 86 KB / 45 KB / 24 KB per workgroup)
-    // (kOcc8: eight workgroups of four waves per CU, 64 VGPRs)
-    static constexpr int kMinWavesPerSimd = BLOCK >= 1024 ? 4 : (BLOCK >= 512 ? 6 : (kOcc8<BLOCK, ABL> ? 8 : 7));
+    // waves per SIMD to reserve registers for: seven workgroups of four waves per CU
+    // (kOcc8: eight, 64 VGPRs)
+    static constexpr int kMinWavesPerSimd = kOcc8<ABL> ? 8 : 7;
     static constexpr int kMaxWavesPerSimd = 8;
     static constexpr int kMaxVgpr = 512 / kMinWavesPerSimd / 8 * 8;   // 72 for 7 waves per SIMD
 };
@@ -1429,10 +1211,10 @@ struct TileIn {
     uint4 hv;
 };
 
-template <int BLOCK, unsigned ABL>
+template <unsigned ABL>
 __device__ __forceinline__ void tile_issue(const RouteParams &p, uint32_t bi, uint32_t t, TileIn &in, int tid) {
-    constexpr int kTileB = BLOCK * kLaneBytes;
-    constexpr int kHalo = SmemT<BLOCK, kOcc8<BLOCK, ABL>>::kHalo;
+    constexpr int kTileB = kTile;
+    constexpr int kHalo = SmemT<kOcc8<ABL>>::kHalo;
     const BatchDesc &bd = p.b[bi];
     const uint32_t T0 = t * (uint32_t)kTileB;
     const __amdgpu_buffer_rsrc_t rsrc =
@@ -1471,7 +1253,7 @@ __device__ __forceinline__ void prefetch_sink(uint32_t v) { asm volatile("" ::"v
 // the registers of `in` into the LDS image (thread tid's chunk = image row tid), the '\n' / ':'
 // masks of the thread's 64 bytes (bit i = byte 64 tid + i) into nlm / clm, and the tile's '\n'
 // count published for the scanner.
-template <int BLOCK, unsigned ABL, class S>
+template <unsigned ABL, class S>
 __device__ __forceinline__ void tile_load(const RouteParams &p, S &sm, const TileIn &in, uint32_t epoch,
                                           uint32_t g, uint64_t &nlm, uint64_t &clm, uint32_t &c_in) {
     constexpr int kWaves = S::kWaves;
@@ -1496,12 +1278,7 @@ __device__ __forceinline__ void tile_load(const RouteParams &p, S &sm, const Til
         ds_write2_at<14, 15>(rb, in.v[3].z, in.v[3].w);
         uint32_t m[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (ABL & ABL_OLD_MASKS)
-                m[k] = eq_mask16_dot(in.v[k], 0x0A0A0A0Au) | (eq_mask16_dot(in.v[k], 0x3A3A3A3Au) << 16);
-            else
-                m[k] = nl_colon_mask16(in.v[k]);
-        }
+        for (int k = 0; k < 4; ++k) m[k] = nl_colon_mask16(in.v[k]);
         nlm = ((uint64_t)__builtin_amdgcn_perm(m[3], m[2], 0x05040100u) << 32) |
               __builtin_amdgcn_perm(m[1], m[0], 0x05040100u);
         clm = ((uint64_t)__builtin_amdgcn_perm(m[3], m[2], 0x07060302u) << 32) |
@@ -1516,15 +1293,14 @@ __device__ __forceinline__ void tile_load(const RouteParams &p, S &sm, const Til
     for (int w = 0; w < kWaves; ++w) tile_count += sm.wave_cnt[w];
     if (tid == 0) {   // publish this tile's '\n' count for the scanner
         const uint32_t x = xcc_id();
-        const bool same = !(ABL & ABL_AGENT_GRANULES) && granule_ok(in.sx, epoch & 0x3FFFFFFFu, kFlagXcc) &&
-                          (uint32_t)in.sx == x;
+        const bool same = granule_ok(in.sx, epoch & 0x3FFFFFFFu, kFlagXcc) && (uint32_t)in.sx == x;
         granule_store(&status[in.t], mk_status(epoch, kFlagAgg, tile_count | ((8u | x) << 28)), same);
     }
 }
 
 // Second half: lines, hashes, shards and records of the tile whose bytes tile_load left in the
 // LDS image and whose chunk masks are in nlm / clm.
-template <int BLOCK, unsigned ABL, class S>
+template <unsigned ABL, class S>
 __device__ __forceinline__ void tile_lines(const RouteParams &p, S &sm, const TileIn &in, uint32_t epoch,
                                            uint32_t g, uint64_t nlm, uint64_t clm, uint32_t c_in) {
     stamp<ABL>(p, threadIdx.x, g, 1);
@@ -1721,11 +1497,10 @@ __device__ __forceinline__ void tile_lines(const RouteParams &p, S &sm, const Ti
     for (int wbase = 0; wbase < (int)tile_count;) {
         wg_barrier();
         if (wbase == 0) stamp<ABL>(p, tid, g, 4);
-        // the tile's record base is read when the first record is written (ABL_EARLY_BASE: also
-        // here); the pipelined scanner has normally published it well before
+        // the tile's record base is read part-way through the first hash (sdbm_img, into st_early) and,
+        // if not published by then, waited for when the first record is written; the pipelined scanner
+        // has normally published it well before
         uint64_t st_early = 0;
-        if (!have_base && (ABL & ABL_EARLY_BASE))
-            st_early = __hip_atomic_load(base_slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (!(ABL & ABL_NO_LINES)) {
             const int s_pre = sm.s_pre;
             const int c_pre = sm.c_pre;
@@ -1790,9 +1565,8 @@ __device__ __forceinline__ void tile_lines(const RouteParams &p, S &sm, const Ti
                     const int n = c - s, nseg = (n + 63) >> 6;
                     for (int k = gi; k < nseg; k += Gl) {
                         const int a = s + 64 * k, nn = min(64, n - 64 * k);
-                        const bool mid = !(ABL & (ABL_NO_MID_BASE | ABL_EARLY_BASE)) && !have_base && k == gi;
-                        uint64_t hs = (ABL & ABL_OLD_HASH) ? sdbm_lds(sm, a + kHalo, nn)
-                                                           : sdbm_img(sm, a + kHalo, nn, mid ? base_slot : nullptr, &st_early);
+                        const bool mid = !(ABL & ABL_NO_MID_BASE) && !have_base && k == gi;
+                        uint64_t hs = sdbm_img(sm, a + kHalo, nn, mid ? base_slot : nullptr, &st_early);
                         if (k + 1 < nseg) hs *= kpow_n(sm, c - a - nn);   // the last segment ends at c
                         h += hs;
                     }
@@ -1859,8 +1633,8 @@ __device__ __forceinline__ void tile_lines(const RouteParams &p, S &sm, const Ti
                 // then runs on the one or two waves that hold those segments, the others only meet
                 // its barriers; two-segment lanes everywhere cost 3 waves x 2 segments instead.)
                 const uint32_t mxs = (uint32_t)__builtin_amdgcn_readfirstlane(mx);
-                const int cost_u = ((nwin * G + BLOCK - 1) / BLOCK) * (int)((mxs + (uint32_t)G - 1) / (uint32_t)G);
-                const int cost_s = ((int)TL + BLOCK - 1) / BLOCK;
+                const int cost_u = ((nwin * G + kBlock - 1) / kBlock) * (int)((mxs + (uint32_t)G - 1) / (uint32_t)G);
+                const int cost_s = ((int)TL + kBlock - 1) / kBlock;
                 segs = cost_s < cost_u;
                 gain2 = cost_s + 2 <= cost_u;
                 if (segs) {
@@ -1883,22 +1657,18 @@ __device__ __forceinline__ void tile_lines(const RouteParams &p, S &sm, const Ti
                     __hip_atomic_fetch_add(&p.ctl->layout[g & 7u][1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             if (!segs) {
-                for (int r0 = 0; r0 < nwin * G; r0 += BLOCK) {
+                for (int r0 = 0; r0 < nwin * G; r0 += kBlock) {
                     const uint32_t x = (uint32_t)(r0 + tid);
                     const int jj = (int)(x >> __builtin_ctz((unsigned)G));
                     line(jj, jj < nwin, (int)(x & (uint32_t)(G - 1)), G, G);
                 }
             } else if constexpr ((ABL & KV_SEGMENTS) != 0) {
-                for (int r0 = 0; r0 < (int)TL; r0 += BLOCK) {
+                for (int r0 = 0; r0 < (int)TL; r0 += kBlock) {
                     const uint32_t x = (uint32_t)(r0 + tid);
                     const uint32_t k = x >> 6;   // the lane word: wave-uniform
                     const bool act = x < TL;
                     // a wave without a segment in this round only meets the barrier
-                    const bool live = r0 + wave * 64 < (int)TL
-#ifdef SR_SEG_ONE_ROUND   // timing bound only (wrong records): no segment work past a tile's first round
-                                      && r0 == 0
-#endif
-                        ;
+                    const bool live = r0 + wave * 64 < (int)TL;
                     uint64_t below = 0, part = 0;
                     int sg = 0, glast = -1, j = 0, s = 0, len = 0;
                     bool len_ok = false, fmt_ok = false;
@@ -1971,19 +1741,18 @@ __device__ __forceinline__ void tile_lines(const RouteParams &p, S &sm, const Ti
     stamp<ABL>(p, tid, g, 6);
 }
 
+// The kernel's first template argument is always kBlock. Nothing reads it: it stays in the signature
+// because the kernels' symbol names (route_kernel<256, mask>) are what the library's tests and the
+// saved profiles identify the variants by.
 template <int BLOCK, unsigned ABL>
-__global__ __launch_bounds__(BLOCK, (KernelTraits<BLOCK, ABL>::kMinWavesPerSimd))
-__attribute__((amdgpu_waves_per_eu((KernelTraits<BLOCK, ABL>::kMinWavesPerSimd), (KernelTraits<BLOCK, ABL>::kMaxWavesPerSimd)))) void route_kernel(RouteParams p) {
-    using S = SmemT<BLOCK, kOcc8<BLOCK, ABL>>;
+__global__ __launch_bounds__(kBlock, (KernelTraits<ABL>::kMinWavesPerSimd))
+__attribute__((amdgpu_waves_per_eu((KernelTraits<ABL>::kMinWavesPerSimd), (KernelTraits<ABL>::kMaxWavesPerSimd)))) void route_kernel(RouteParams p) {
+    static_assert(BLOCK == kBlock, "one workgroup size");
+    using S = SmemT<kOcc8<ABL>>;
     __shared__ S sm;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
-    if (ABL & ABL_LDS_PAD) {   // occupancy experiment: 4 KiB more LDS per workgroup
-        __shared__ uint32_t pad[1024];
-        if (p.nb > 1000000u) pad[tid] = tid;   // never true: keeps the array
-        if (p.nb > 1000000u) p.ctl->pad1 = pad[(tid + 1) & 1023];
-    }
     uint4 hdr;
     const uint32_t bi = launch_header_batch(hdr);
     if (blockIdx.x < hdr.x) {   // scanner of batch blockIdx.x (wave 0; no barriers on this path)
@@ -1993,21 +1762,16 @@ __attribute__((amdgpu_waves_per_eu((KernelTraits<BLOCK, ABL>::kMinWavesPerSimd),
         // the batch's probed-dead bitmap starts empty (set after this launch by probe_defer_kernel,
         // probe_wide_kernel or probed_dead_kernel, sr-main.c:106; with every shard alive it stays empty)
         if (uint64_t *pd = p.b[blockIdx.x].probed_dead)
-            for (uint32_t w = tid; w < p.nwords; w += BLOCK) pd[w] = 0ull;
+            for (uint32_t w = tid; w < p.nwords; w += kBlock) pd[w] = 0ull;
         const uint32_t ep0 = __hip_atomic_load(&p.ctl->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (ABL & ABL_OLD_SCANNER) {
-            if (wave == 0) scan_batch<BLOCK>(p, p.b[blockIdx.x], ep0, lane);
-            if (tid == 0) arrive(p, blockIdx.x, ep0);
-        } else {
-            if (tid == 0) {
-                sm.scan_head = 0;
-                sm.scan_pub = 0;
-                sm.scan_total = 0;
-            }
-            wg_barrier();
-            scan_batch_split<BLOCK, ABL>(p, p.b[blockIdx.x], ep0, sm, wave, lane);
-            if (tid == 64) arrive(p, blockIdx.x, ep0);   // the publisher, after its last store
+        if (tid == 0) {
+            sm.scan_head = 0;
+            sm.scan_pub = 0;
+            sm.scan_total = 0;
         }
+        wg_barrier();
+        scan_batch_split<ABL>(p, p.b[blockIdx.x], ep0, sm, wave, lane);
+        if (tid == 64) arrive(p, blockIdx.x, ep0);   // the publisher, after its last store
         return;
     }
     const uint32_t g = blockIdx.x - hdr.x;   // tile workgroup index within the launch
@@ -2029,13 +1793,12 @@ __attribute__((amdgpu_waves_per_eu((KernelTraits<BLOCK, ABL>::kMinWavesPerSimd),
     // the count publish and the hash) queue behind them
     const uint32_t t = (hdr.z ? (g >> 3) : g) - p.b[bi].tile0;   // the tile's index in its batch
     TileIn in;
-    tile_issue<BLOCK, ABL>(p, bi, t, in, tid);
+    tile_issue<ABL>(p, bi, t, in, tid);
     const uint32_t kp = tid < S::kPowWords ? ((const uint32_t *)p.kpow)[tid] : 0u;
     // the scanner granule's load before the epoch's: the epoch's value is wanted at once (a wait for
     // every load issued before it, vmcnt counts in order), and a granule load issued after that wait
     // is a whole round trip more before the tile can publish its count (+5 % per C2 launch measured)
-    in.sx = (ABL & ABL_AGENT_GRANULES) ? 0ull
-                                       : __hip_atomic_load(&p.ctl->scan_xcc[bi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    in.sx = __hip_atomic_load(&p.ctl->scan_xcc[bi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t ep0 = __hip_atomic_load(&p.ctl->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (kEarlyArrive<ABL> && tid == 0) arrive_count_after(p, blockIdx.x, ep0);
     if (tid < S::kPowWords) sm.put_pow(tid, kp);
@@ -2052,8 +1815,8 @@ __attribute__((amdgpu_waves_per_eu((KernelTraits<BLOCK, ABL>::kMinWavesPerSimd),
     if (kCountsHist<ABL> && p.hist && tid < kHistKeys) sm.hist[tid] = 0u;
     uint64_t nlm, clm;
     uint32_t c_in;
-    tile_load<BLOCK, ABL>(p, sm, in, ep0, g, nlm, clm, c_in);
-    tile_lines<BLOCK, ABL>(p, sm, in, ep0, g, nlm, clm, c_in);
+    tile_load<ABL>(p, sm, in, ep0, g, nlm, clm, c_in);
+    tile_lines<ABL>(p, sm, in, ep0, g, nlm, clm, c_in);
     mark_tile_end<ABL>(p, sm.img, p.b[bi], t, tid);   // MARK_LDS: the dead shards this tile's probes visited
     if (kCountsHist<ABL> && p.hist) {   // the tile's key histogram for the packing (sr_route_pack_many)
         wg_barrier();

@@ -108,15 +108,15 @@ static void free_ptr(void *p) { (void)hipFree(p); }
 static int launch_product(DeviceState &ds, const RouteParams &p, hipStream_t stream) {
     const bool seg = ds.choose_segments(stream);
     if (ds.last_layout == SR_LAYOUT_CHUNKS) {
-        if (ds.dead == 0) return launch_route<kBlock, KV_CHUNKS | KV_ALIVE | SR_CHUNK_ABL>(ds, p, stream);
-        return launch_route<kBlock, KV_CHUNKS | SR_CHUNK_ABL>(ds, p, stream);
+        if (ds.dead == 0) return launch_route<KV_CHUNKS | KV_ALIVE | SR_CHUNK_ABL>(ds, p, stream);
+        return launch_route<KV_CHUNKS | SR_CHUNK_ABL>(ds, p, stream);
     }
     if (ds.dead == 0) {   // every shard alive: the variants without the probe
-        if (seg) return launch_route<kBlock, KV_SEGMENTS | KV_ALIVE>(ds, p, stream);
-        return launch_route<kBlock, KV_UNIFORM | KV_ALIVE>(ds, p, stream);
+        if (seg) return launch_route<KV_SEGMENTS | KV_ALIVE>(ds, p, stream);
+        return launch_route<KV_UNIFORM | KV_ALIVE>(ds, p, stream);
     }
-    if (seg) return launch_route<kBlock, KV_SEGMENTS | KV_PICKS>(ds, p, stream);
-    return launch_route<kBlock, KV_UNIFORM | KV_PICKS>(ds, p, stream);
+    if (seg) return launch_route<KV_SEGMENTS | KV_PICKS>(ds, p, stream);
+    return launch_route<KV_UNIFORM | KV_PICKS>(ds, p, stream);
 }
 #ifdef SR_ABLATION_VARIANTS
 static int launch_variant(DeviceState &ds, const RouteParams &p, hipStream_t stream) {
@@ -131,10 +131,10 @@ static int launch_variant(DeviceState &ds, const RouteParams &p, hipStream_t str
         return 0;
     }();
     switch (v) {
-    case 14: return launch_route<kBlock, ABL_NO_MID_BASE>(ds, p, stream);
-    case 7: return launch_route<kBlock, ABL_FAKE_BASE>(ds, p, stream);
-    case 8: return launch_route<kBlock, ABL_NO_HASH>(ds, p, stream);
-    case 9: return launch_route<kBlock, ABL_NO_LINES>(ds, p, stream);
+    case 14: return launch_route<ABL_NO_MID_BASE>(ds, p, stream);
+    case 7: return launch_route<ABL_FAKE_BASE>(ds, p, stream);
+    case 8: return launch_route<ABL_NO_HASH>(ds, p, stream);
+    case 9: return launch_route<ABL_NO_LINES>(ds, p, stream);
     default: return launch_product(ds, p, stream);
     }
 }

@@ -1,6 +1,6 @@
 // Ablation of route_kernel on the bench workloads (16 MiB batches of L-byte metrics, 4 shards).
-// Every variant is an instantiation of the same kernel template (route_kernel.hpp: BLOCK threads
-// per workgroup, ABL_* parts switched off). Variants are timed in interleaved rounds in ONE
+// Every variant is an instantiation of the same kernel template (route_kernel.hpp: ABL_* parts
+// switched off). Variants are timed in interleaved rounds in ONE
 // process over the same rotating set of 64 distinct batches, launched back to back from a
 // hipGraph, on S concurrent streams (each stream with its own context state). A plain
 // streaming-read kernel gives the achievable read rate for the same batches.
@@ -55,7 +55,7 @@ struct Ctx {
 };
 
 // S streams, M batches per launch (launch i routes batches i*M .. i*M+M-1 on stream i % S)
-template <int BLOCK, unsigned V>
+template <unsigned V>
 float time_variant(Ctx &c, int S, int reps, int M = 1) {
     const int B = (int)c.batches.size();
     auto launch = [&](int i) {
@@ -70,7 +70,7 @@ float time_variant(Ctx &c, int S, int reps, int M = 1) {
                 const int k = (i * M + m) % B;
                 DeviceState::add_batch(p, c.batches[k], c.sizes[k], c.d_out[st][m % 16], c.max_lines, nullptr, c.d_n + k);
             }
-            launch_route<BLOCK, V>(c.ds[st], p, c.s[st]);
+            launch_route<V>(c.ds[st], p, c.s[st]);
         }
     };
     hipGraph_t g;
@@ -152,79 +152,52 @@ int main(int argc, char **argv) {
             rows[i++].us[round] = us;
         };
         if (alive) {
-            put("alive", time_variant<256, KV_ALIVE>(c, 1, reps, 32));
-            put("alive_no_hash", time_variant<256, KV_ALIVE | ABL_NO_HASH>(c, 1, reps, 32));
-            put("alive_no_lines", time_variant<256, KV_ALIVE | ABL_NO_LINES>(c, 1, reps, 32));
-            put("alive_no_lines_no_prologue", time_variant<256, KV_ALIVE | ABL_NO_LINES | ABL_NO_PROLOGUE>(c, 1, reps, 32));
-            put("alive_load_only", time_variant<256, KV_ALIVE | ABL_LOAD_ONLY | ABL_NO_LOOKBACK | ABL_NO_PROLOGUE>(c, 1, reps, 32));
-            put("alive_fake_base", time_variant<256, KV_ALIVE | ABL_FAKE_BASE>(c, 1, reps, 32));
-            put("read_kernel_s1", time_variant<256, 0xFFFFu>(c, 1, reps));
+            put("alive", time_variant<KV_ALIVE>(c, 1, reps, 32));
+            put("alive_no_hash", time_variant<KV_ALIVE | ABL_NO_HASH>(c, 1, reps, 32));
+            put("alive_no_lines", time_variant<KV_ALIVE | ABL_NO_LINES>(c, 1, reps, 32));
+            put("alive_no_lines_no_prologue", time_variant<KV_ALIVE | ABL_NO_LINES | ABL_NO_PROLOGUE>(c, 1, reps, 32));
+            put("alive_load_only", time_variant<KV_ALIVE | ABL_LOAD_ONLY | ABL_NO_LOOKBACK | ABL_NO_PROLOGUE>(c, 1, reps, 32));
+            put("alive_fake_base", time_variant<KV_ALIVE | ABL_FAKE_BASE>(c, 1, reps, 32));
+            put("read_kernel_s1", time_variant<0xFFFFu>(c, 1, reps));
             continue;
         }
         if (quick) {
-            put("m32", time_variant<256, ABL_NONE>(c, 1, reps, 32));
-            put("m32_fake_base", time_variant<256, ABL_FAKE_BASE>(c, 1, reps, 32));
-            put("m32_early_base", time_variant<256, ABL_EARLY_BASE>(c, 1, reps, 32));
-            put("m32_no_mid_base", time_variant<256, ABL_NO_MID_BASE>(c, 1, reps, 32));
-            put("m32_no_lookback", time_variant<256, ABL_NO_LOOKBACK>(c, 1, reps, 32));
-            put("m32_no_hash", time_variant<256, ABL_NO_HASH>(c, 1, reps, 32));
-            put("m32_no_prologue", time_variant<256, ABL_NO_PROLOGUE>(c, 1, reps, 32));
-            put("m32_no_lines", time_variant<256, ABL_NO_LINES>(c, 1, reps, 32));
-            put("m32_load_only", time_variant<256, ABL_LOAD_ONLY | ABL_NO_LOOKBACK | ABL_NO_PROLOGUE>(c, 1, reps, 32));
-            put("read_kernel_s1", time_variant<256, 0xFFFFu>(c, 1, reps));
+            put("m32", time_variant<ABL_NONE>(c, 1, reps, 32));
+            put("m32_fake_base", time_variant<ABL_FAKE_BASE>(c, 1, reps, 32));
+            put("m32_no_mid_base", time_variant<ABL_NO_MID_BASE>(c, 1, reps, 32));
+            put("m32_no_lookback", time_variant<ABL_NO_LOOKBACK>(c, 1, reps, 32));
+            put("m32_no_hash", time_variant<ABL_NO_HASH>(c, 1, reps, 32));
+            put("m32_no_prologue", time_variant<ABL_NO_PROLOGUE>(c, 1, reps, 32));
+            put("m32_no_lines", time_variant<ABL_NO_LINES>(c, 1, reps, 32));
+            put("m32_load_only", time_variant<ABL_LOAD_ONLY | ABL_NO_LOOKBACK | ABL_NO_PROLOGUE>(c, 1, reps, 32));
+            put("read_kernel_s1", time_variant<0xFFFFu>(c, 1, reps));
             continue;
         }
-        put("b256_m16_lds_pad", time_variant<256, ABL_LDS_PAD>(c, 1, reps, 16));
-        put("b256_m16_scan_serial", time_variant<256, ABL_SCAN_SERIAL>(c, 1, reps, 16));
-        put("b256_m16_agent_granules", time_variant<256, ABL_AGENT_GRANULES>(c, 1, reps, 16));
-        put("b256_m16_old_masks", time_variant<256, ABL_OLD_MASKS>(c, 1, reps, 16));
-        put("b256_m16_old_scanner", time_variant<256, ABL_OLD_SCANNER>(c, 1, reps, 16));
-        put("b256_m16_fake_base", time_variant<256, ABL_FAKE_BASE>(c, 1, reps, 16));
-        put("b256_m16_fake_base_no_hash", time_variant<256, ABL_FAKE_BASE | ABL_NO_HASH>(c, 1, reps, 16));
-        put("b256_m16_early_base", time_variant<256, ABL_EARLY_BASE>(c, 1, reps, 16));
-        put("b256_m16_old_hash", time_variant<256, ABL_OLD_HASH>(c, 1, reps, 16));
-        put("b256_m16_old_hash_no_lookback", time_variant<256, ABL_OLD_HASH | ABL_NO_LOOKBACK>(c, 1, reps, 16));
-        put("b256_m16_no_hash_no_lookback", time_variant<256, ABL_NO_HASH | ABL_NO_LOOKBACK>(c, 1, reps, 16));
-        put("b256_m16_no_hash_no_prologue", time_variant<256, ABL_NO_HASH | ABL_NO_PROLOGUE>(c, 1, reps, 16));
-        put("b512_m16", time_variant<512, ABL_NONE>(c, 1, reps, 16));
-        put("b256_m16_no_hash", time_variant<256, ABL_NO_HASH>(c, 1, reps, 16));
-        put("b512_m16_no_hash", time_variant<512, ABL_NO_HASH>(c, 1, reps, 16));
-        put("b256_m16", time_variant<256, ABL_NONE>(c, 1, reps, 16));
-        put("b512_m16_no_lookback", time_variant<512, ABL_NO_LOOKBACK>(c, 1, reps, 16));
-        put("b512_m16_no_lines", time_variant<512, ABL_NO_LINES>(c, 1, reps, 16));
-        put("b512_m16_load_only", time_variant<512, ABL_LOAD_ONLY | ABL_NO_LOOKBACK | ABL_NO_PROLOGUE>(c, 1, reps, 16));
-        put("b256_m16_no_lookback", time_variant<256, ABL_NO_LOOKBACK>(c, 1, reps, 16));
-        put("b256_m16_no_lines", time_variant<256, ABL_NO_LINES>(c, 1, reps, 16));
-        put("b256_m16_load_only", time_variant<256, ABL_LOAD_ONLY | ABL_NO_LOOKBACK | ABL_NO_PROLOGUE>(c, 1, reps, 16));
-        put("b256_m1", time_variant<256, ABL_NONE>(c, 1, reps, 1));
-        put("read_kernel_s1", time_variant<256, 0xFFFFu>(c, 1, reps));
-        put("read_kernel_s4", time_variant<256, 0xFFFFu>(c, 4, reps));
+        put("b256_m16_fake_base", time_variant<ABL_FAKE_BASE>(c, 1, reps, 16));
+        put("b256_m16_fake_base_no_hash", time_variant<ABL_FAKE_BASE | ABL_NO_HASH>(c, 1, reps, 16));
+        put("b256_m16_no_hash_no_lookback", time_variant<ABL_NO_HASH | ABL_NO_LOOKBACK>(c, 1, reps, 16));
+        put("b256_m16_no_hash_no_prologue", time_variant<ABL_NO_HASH | ABL_NO_PROLOGUE>(c, 1, reps, 16));
+        put("b256_m16_no_hash", time_variant<ABL_NO_HASH>(c, 1, reps, 16));
+        put("b256_m16", time_variant<ABL_NONE>(c, 1, reps, 16));
+        put("b256_m16_no_lookback", time_variant<ABL_NO_LOOKBACK>(c, 1, reps, 16));
+        put("b256_m16_no_lines", time_variant<ABL_NO_LINES>(c, 1, reps, 16));
+        put("b256_m16_load_only", time_variant<ABL_LOAD_ONLY | ABL_NO_LOOKBACK | ABL_NO_PROLOGUE>(c, 1, reps, 16));
+        put("b256_m1", time_variant<ABL_NONE>(c, 1, reps, 1));
+        put("read_kernel_s1", time_variant<0xFFFFu>(c, 1, reps));
+        put("read_kernel_s4", time_variant<0xFFFFu>(c, 4, reps));
     }
-    // correctness: each product-shaped variant's line count on batch 0
-    if (!quick && !alive) {
-        uint64_t n = 0;
-        const RouteParams p = c.ds[0].params(c.batches[0], c.sizes[0], c.d_out[0][0], c.max_lines, nullptr, c.d_n);
-        launch_route<1024, ABL_NONE>(c.ds[0], p, c.s[0]);
-        CK(hipMemcpyAsync(&n, c.d_n, 8, hipMemcpyDeviceToHost, c.s[0]));
-        CK(hipStreamSynchronize(c.s[0]));
-        fprintf(stderr, "b1024 lines %llu expected %zu\n", (unsigned long long)n, lines[0]);
-        launch_route<512, ABL_NONE>(c.ds[0], p, c.s[0]);
-        CK(hipMemcpyAsync(&n, c.d_n, 8, hipMemcpyDeviceToHost, c.s[0]));
-        CK(hipStreamSynchronize(c.s[0]));
-        fprintf(stderr, "b512 lines %llu expected %zu\n", (unsigned long long)n, lines[0]);
-    }
-    if (!quick && !alive) {   // multi-batch launch: every batch's line count
+    if (!quick && !alive) {   // correctness, multi-batch launch: every batch's line count
         std::vector<uint64_t> n(16);
         RouteParams p = c.ds[0].params();
         for (int k = 0; k < 16; ++k)
             DeviceState::add_batch(p, c.batches[k], c.sizes[k], c.d_out[0][0], c.max_lines, nullptr, c.d_n + k);
         CK(hipMemsetAsync(c.d_n, 0xFF, 16 * 8, c.s[0]));
-        launch_route<512, ABL_NONE>(c.ds[0], p, c.s[0]);
+        launch_route<ABL_NONE>(c.ds[0], p, c.s[0]);
         CK(hipMemcpyAsync(n.data(), c.d_n, 16 * 8, hipMemcpyDeviceToHost, c.s[0]));
         CK(hipStreamSynchronize(c.s[0]));
         int bad = 0;
         for (int k = 0; k < 16; ++k) bad += n[k] != lines[k];
-        fprintf(stderr, "b512 m16: %d of 16 batch counts wrong\n", bad);
+        fprintf(stderr, "b256 m16: %d of 16 batch counts wrong\n", bad);
     }
     printf("{\"line_len\": %u, \"batch_bytes\": %zu, \"us_per_batch\": {", line_len, batch);
     for (size_t r = 0; r < rows.size(); ++r) {

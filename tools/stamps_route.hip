@@ -34,11 +34,10 @@ static double med(std::vector<double> v) {
 // workgroup of the launch, plus the launch span
 static bool seg_layout = false, chunk_layout = false;
 
-template <int BLOCK>
 void run_many(DeviceState &ds, std::vector<uint8_t *> &batches, std::vector<size_t> &sizes, sr_record *d_out,
               size_t max_lines, uint64_t *d_n, uint64_t *d_dbg, hipStream_t s, uint32_t line_len) {
     const int L = (int)batches.size();
-    const uint32_t T = BLOCK * kLaneBytes;
+    const uint32_t T = kTile;
     uint32_t total = 0;
     for (int i = 0; i < L; ++i) total += (uint32_t)((sizes[i] + T - 1) / T);
     std::vector<uint64_t> h((size_t)total * 16);
@@ -47,9 +46,9 @@ void run_many(DeviceState &ds, std::vector<uint8_t *> &batches, std::vector<size
         for (int i = 0; i < L; ++i)
             DeviceState::add_batch(p, batches[i], sizes[i], d_out + (size_t)i * max_lines, max_lines, nullptr, d_n + i);
         p.dbg = d_dbg;
-        if (chunk_layout) launch_route<BLOCK, ABL_STAMPS | KV_CHUNKS | KV_ALIVE>(ds, p, s);
-        else if (seg_layout) launch_route<BLOCK, ABL_STAMPS | KV_SEGMENTS | KV_ALIVE>(ds, p, s);
-        else launch_route<BLOCK, ABL_STAMPS | KV_ALIVE>(ds, p, s);
+        if (chunk_layout) launch_route<ABL_STAMPS | KV_CHUNKS | KV_ALIVE>(ds, p, s);
+        else if (seg_layout) launch_route<ABL_STAMPS | KV_SEGMENTS | KV_ALIVE>(ds, p, s);
+        else launch_route<ABL_STAMPS | KV_ALIVE>(ds, p, s);
     };
     for (int w = 0; w < 3; ++w) launch();
     CK(hipStreamSynchronize(s));
@@ -105,21 +104,6 @@ void run_many(DeviceState &ds, std::vector<uint8_t *> &batches, std::vector<size
             fclose(f);
         }
     }
-    {   // scanner poll rounds (batch 0 and 8): round-trip percentiles and round count
-        std::vector<uint64_t> sc(16 * 4096);
-        CK(hipMemcpy(sc.data(), d_dbg + 300000, 16 * 4096 * 8, hipMemcpyDeviceToHost));
-        std::vector<double> rt;
-        int nr = 0;
-        for (int b = 0; b < 16; ++b)
-            for (int r = 0; r < 2048; ++r) {
-                const uint64_t a = sc[b * 4096 + 2 * r], z = sc[b * 4096 + 2 * r + 1];
-                if (a && z) rt.push_back((double)(z - a) * 0.01), ++nr;
-            }
-        std::sort(rt.begin(), rt.end());
-        if (!rt.empty())
-            printf("{\"scanner_poll_rt_us\": [%.2f, %.2f, %.2f, %.2f], \"rounds_per_batch\": %.1f}\n", rt[rt.size() / 10],
-                   rt[rt.size() / 2], rt[rt.size() * 9 / 10], rt[rt.size() * 99 / 100], nr / 16.0);
-    }
     std::vector<double> ph[8], ph3b;
     uint64_t s0 = ~0ull, e1 = 0;
     {   // residency: tiles alive over the launch (start stamp 0 .. end stamp 6), in 1 us bins
@@ -164,8 +148,8 @@ void run_many(DeviceState &ds, std::vector<uint8_t *> &batches, std::vector<size
         }
         hipFuncAttributes fa{};
         const void *fn = chunk_layout ? (const void *)route_chunk_kernel<ABL_STAMPS | KV_CHUNKS | KV_ALIVE>
-                         : seg_layout ? (const void *)route_kernel<BLOCK, ABL_STAMPS | KV_SEGMENTS | KV_ALIVE>
-                                      : (const void *)route_kernel<BLOCK, ABL_STAMPS | KV_ALIVE>;
+                         : seg_layout ? (const void *)route_kernel<kBlock, ABL_STAMPS | KV_SEGMENTS | KV_ALIVE>
+                                      : (const void *)route_kernel<kBlock, ABL_STAMPS | KV_ALIVE>;
         CK(hipFuncGetAttributes(&fa, fn));
         printf("{\"residency\": {\"span_us\": %.2f, \"mean_resident_tiles\": %.1f, \"max_resident_per_cu\": %d, "
                "\"cus\": %d, \"cus_at_max\": %d, \"stamps_build\": {\"vgprs\": %d, \"lds_bytes\": %zu, "
@@ -201,7 +185,7 @@ void run_many(DeviceState &ds, std::vector<uint8_t *> &batches, std::vector<size
     printf("{\"mode\": \"%d batches per launch\", \"block\": %d, \"line_len\": %u, \"tiles\": %u, \"span_us\": %.2f, "
            "\"median_us\": {\"load\": %.2f, \"masks_scan\": %.2f, \"base_wait\": %.2f, \"to_staged\": %.2f, "
            "\"hash_records\": %.2f, \"of_which_prepass\": %.2f, \"lifetime\": %.2f, \"entry\": %.2f, \"entry_to_exit\": %.2f}}\n",
-           L, BLOCK, line_len, total, (e1 - s0) * 0.01, med(ph[0]), med(ph[1]), med(ph[2]), med(ph[3]), med(ph[4]),
+           L, kBlock, line_len, total, (e1 - s0) * 0.01, med(ph[0]), med(ph[1]), med(ph[2]), med(ph[3]), med(ph[4]),
            med(ph3b), med(ph[5]), med(ph[6]), med(ph[7]));
 }
 
@@ -241,6 +225,6 @@ int main(int argc, char **argv) {
     CK(hipMalloc(&d_dbg, (size_t)L * 4096 * 16 * 8));
     hipStream_t s;
     CK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    run_many<256>(ds, batches, sizes, d_out, nl, d_n, d_dbg, s, line_len);
+    run_many(ds, batches, sizes, d_out, nl, d_n, d_dbg, s, line_len);
     return 0;
 }
