@@ -209,7 +209,7 @@ int sr_pack_owner_scatter(sr_ctx *ctx, const sr_batch *batches, size_t count, ui
                           uint8_t *d_own_bytes, sr_record *d_own_recs, uint8_t *d_out_bytes, size_t out_cap,
                           sr_record *d_out_recs);
 
-/* ---- multi-GPU exchange of owner packs (RCCL over xGMI) -------------------------------------- */
+/* ---- multi-GPU exchange of owner packs (RCCL over xGMI, or in process) ----------------------- */
 /* One process per GPU; shard s is owned by GPU s % world. After sr_pack_by_owner /
  * sr_pack_many_by_owner (n_owners = world), two collective calls per route launch move every
  * owner's lines to it. RCCL is loaded at sr_comm_open (dlopen of librccl.so.1; a copy already in
@@ -224,13 +224,64 @@ int sr_comm_id(uint8_t id[SR_COMM_ID_BYTES]);
 int sr_comm_open(sr_comm **comm, const uint8_t id[SR_COMM_ID_BYTES], int world, int rank, int device);
 void sr_comm_close(sr_comm *comm);
 
+/* ---- in-process communicator: ranks as threads of one process, no RCCL ------------------------ */
+/* The data threads of one process (the reference's data_pipe_thread's, one per socket, on GPU
+ * i % devices) regroup among themselves without RCCL: everything they need is in one address space,
+ * and RCCL cannot put two ranks on one GPU. A group is the ranks' meeting place (host only, no GPU);
+ * every rank's thread then opens its communicator on it, and that sr_comm works in every call that
+ * takes one (sr_exchange_sizes, sr_exchange_data, sr_regroup_launch, sr_exchange_dead, sr_comm_close):
+ * the calls run the same sequence as on RCCL, only the five collectives underneath differ.
+ *
+ * How it moves data: a sender posts {pointer, bytes, an event recorded on its stream}; the receiver
+ * makes its stream wait for that event and copies every chunk of the group with ONE kernel on its own
+ * stream (a pull), then the sender's stream waits for the pull. Guarantees:
+ *   - stream order as on RCCL: a receive is complete in the receiver's stream order where the group
+ *     ended, and the sender's later work on its stream is ordered after the peers' reads of its buffers;
+ *   - messages between one pair under one tag match in posting order; sizes that differ give -EMSGSIZE
+ *     at the receiver and break the group;
+ *   - the end of a group BLOCKS THE HOST until every peer this rank has operations with has posted and
+ *     pulled (the device work is still asynchronous). So the collectives cannot be captured in a graph:
+ *     a capturing stream returns -EINVAL;
+ *   - nothing is ever enqueued on the device that waits for something not yet recorded: an absent peer
+ *     costs host time only, never a stuck stream.
+ * Ranks on different devices need peer access both ways (enabled at open); that path has not been run
+ * (DESIGN.md §8).
+ *
+ * sr_comm_group_open : world in 1..SR_MAX_OWNERS. Returns 0, -EINVAL, -ENOMEM.
+ * sr_comm_group_close: 0, -EINVAL, or -EBUSY while a communicator of the group is open.
+ * sr_comm_open_local : rank `rank` of the group on HIP device `device`, called once per rank by the
+ *   thread that owns the rank; it does not wait for the other ranks and never needs RCCL. Returns 0,
+ *   -EINVAL (bad rank or group), -ENODEV (bad device), -EBUSY (rank taken), -ENOTSUP (a peer on another
+ *   device without peer access), -ENOMEM. Close with sr_comm_close, before the group.
+ * sr_comm_set_timeout: bounds every host wait of a collective on the comm (RCCL comms: the sequence-
+ *   word spin of sr_exchange_sizes; local comms also the waits for peers) to `ms` milliseconds; 0, the
+ *   default, is no deadline. A wait that runs out returns -ETIMEDOUT and breaks the communicator (a
+ *   local comm: its whole group, whose waiting ranks are woken with -EPIPE); every later collective on
+ *   a broken communicator returns -EPIPE at once; sr_comm_close still works. sr_exchange_sizes has
+ *   one deadline for all of its waits (its all-to-all, then the spin or the stream's drain), `ms`
+ *   from the call. A local collective that fails after it posted its sends still orders the caller's
+ *   stream after every read of those buffers that a peer had enqueued (none is enqueued once the
+ *   group is broken), so they may be reused in stream order. Returns 0 or -EINVAL.
+ * sr_comm_transport  : *out = the communicator as an sr_transport (below) bound to ctx's stream, for
+ *   sr_exchange_run, sr_regroup_run, sr_exchange_dead_run or sends and receives of the caller's own
+ *   (tags 0..2). out->user belongs to the comm and is valid until the next sr_comm_transport on it or
+ *   its close. Returns 0 or -EINVAL. */
+typedef struct sr_comm_group sr_comm_group;
+struct sr_transport;
+int sr_comm_group_open(sr_comm_group **g, int world);
+int sr_comm_group_close(sr_comm_group *g);
+int sr_comm_open_local(sr_comm **comm, sr_comm_group *g, int rank, int device);
+int sr_comm_set_timeout(sr_comm *comm, uint32_t ms);
+int sr_comm_transport(sr_comm *comm, sr_ctx *ctx, struct sr_transport *out);
+
 /* Collective, on the context's stream: all-to-all of the split sizes d_owner_counts (u64
  * [world][2] {lines, bytes} per owner, the pack's output) into d_recv_counts (u64 [world][2] per
  * source rank; one rank: a device copy, no collective), then both to the host: h_sent / h_received
  * (u64 [world][2]) are valid on return (the launch's one host round trip). One kernel writes them to
  * mapped pinned memory behind a sequence word the host spins on (polling the stream for errors), so the
  * call returns as soon as the sizes land, not when the stream drains: the caller's later work on the
- * context's stream is ordered after them as usual. Returns 0, -EINVAL, -EIO. */
+ * context's stream is ordered after them as usual. The spin has no deadline unless sr_comm_set_timeout
+ * gave the comm one. Returns 0, -EINVAL, -EIO, -ETIMEDOUT / -EPIPE (sr_comm_set_timeout). */
 int sr_exchange_sizes(sr_ctx *ctx, sr_comm *comm, const uint64_t *d_owner_counts, uint64_t *d_recv_counts,
                       uint64_t *h_sent, uint64_t *h_received);
 
@@ -261,7 +312,8 @@ typedef struct sr_exchange_peer {
 int sr_exchange_plan(int world, int rank, const uint64_t *h_sent, const uint64_t *h_received,
                      sr_exchange_peer *peers, uint64_t *totals);
 
-/* The transport an exchange runs on. sr_exchange_data uses RCCL (ncclSend/ncclRecv in one group, the
+/* The transport an exchange runs on. sr_exchange_data uses the communicator's own (sr_comm_transport;
+ * RCCL: ncclSend/ncclRecv in one group, the
  * own chunk by hipMemcpyAsync, the rebase by a kernel, all on the context's stream); a host that moves
  * the chunks another way (tests: torch.distributed gloo over host memory) supplies its own. Every
  * callback returns 0 or a negative errno. tag 0 = line bytes, 1 = records, 2 = a probed-dead bitmap row

@@ -56,6 +56,7 @@ ABI_FUNCTIONS = (
     "sr_set_trace", "sr_route_pack_trace", "sr_set_knob", "sr_route_pack_many", "sr_regroup_run",
     "sr_pack_payloads_many", "sr_pack_payloads", "sr_set_payloads", "sr_route_pack_payloads",
     "sr_exchange_dead_run", "sr_exchange_dead", "sr_owner_pack", "sr_flush_pending",
+    "sr_comm_group_open", "sr_comm_group_close", "sr_comm_open_local", "sr_comm_set_timeout", "sr_comm_transport",
 )
 SR_MAX_PACK_DOWNSTREAMS = 4096
 SR_LAYOUT_AUTO, SR_LAYOUT_UNIFORM, SR_LAYOUT_SEGMENTS, SR_LAYOUT_CHUNKS = 0, 1, 2, 3
@@ -230,6 +231,11 @@ def _load_route_lib() -> ctypes.CDLL:
         "sr_comm_id": (ctypes.c_int, [vp]),
         "sr_comm_open": (ctypes.c_int, [ctypes.POINTER(vp), vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
         "sr_comm_close": (None, [vp]),
+        "sr_comm_group_open": (ctypes.c_int, [ctypes.POINTER(vp), ctypes.c_int]),
+        "sr_comm_group_close": (ctypes.c_int, [vp]),
+        "sr_comm_open_local": (ctypes.c_int, [ctypes.POINTER(vp), vp, ctypes.c_int, ctypes.c_int]),
+        "sr_comm_set_timeout": (ctypes.c_int, [vp, ctypes.c_uint32]),
+        "sr_comm_transport": (ctypes.c_int, [vp, vp, ctypes.POINTER(SrTransport)]),
         "sr_exchange_sizes": (ctypes.c_int, [vp, vp, vp, vp, vp, vp]),
         "sr_exchange_data": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
         "sr_exchange_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]),
@@ -753,8 +759,26 @@ class Router:
         _check(self._lib.sr_sync(self._h), "sr_sync")
 
 
+class CommGroup:
+    """The meeting place of an in-process communicator's ranks (sr_comm_group_open; host only): the threads
+    of one process each open their rank on it with Comm.local. Close it after its communicators."""
+
+    def __init__(self, world: int):
+        self._lib = lib()
+        h = ctypes.c_void_p()
+        _check(self._lib.sr_comm_group_open(ctypes.byref(h), world), "sr_comm_group_open")
+        self.handle, self.world = h, world
+
+    def close(self) -> None:
+        """sr_comm_group_close: raises SrError(EBUSY) while a communicator of the group is open."""
+        if self.handle:
+            _check(self._lib.sr_comm_group_close(self.handle), "sr_comm_group_close")
+            self.handle = ctypes.c_void_p()
+
+
 class Comm:
-    """An RCCL communicator of the C ABI (sr_comm_open): `world` ranks, one GPU each."""
+    """A communicator of the C ABI: RCCL (sr_comm_open: `world` ranks, one GPU each) or, with Comm.local,
+    ranks that are threads of one process (sr_comm_open_local)."""
 
     def __init__(self, comm_id: bytes, world: int, rank: int, device: int):
         self._lib = lib()
@@ -785,6 +809,22 @@ class Comm:
         if isinstance(box[0], str):
             raise RuntimeError(f"rank 0 could not make the communicator id: {box[0]}")
         return cls(box[0], dist.get_world_size(group), dist.get_rank(group), device)
+
+    @classmethod
+    def local(cls, group: CommGroup, rank: int, device: int) -> "Comm":
+        """sr_comm_open_local: rank `rank` of an in-process group, opened by the thread that owns the rank
+        (no RCCL; does not wait for the other ranks)."""
+        self = cls.__new__(cls)
+        self._lib = lib()
+        h = ctypes.c_void_p()
+        _check(self._lib.sr_comm_open_local(ctypes.byref(h), group.handle, rank, device), "sr_comm_open_local")
+        self.handle, self.world, self.rank, self.device, self.group = h, group.world, rank, device, group
+        return self
+
+    def set_timeout(self, ms: int) -> None:
+        """sr_comm_set_timeout: every host wait of a collective on this comm gives up after ms milliseconds
+        (-ETIMEDOUT, the communicator broken: -EPIPE from then on); 0 = no deadline (the default)."""
+        _check(self._lib.sr_comm_set_timeout(self.handle, int(ms)), "sr_comm_set_timeout")
 
     def close(self) -> None:
         if self.handle:
@@ -836,6 +876,46 @@ class Transport:
         for p in peers:
             a, n = int(p["recv_line0"]), int(p["recv_lines"])
             recs["offset"][a: a + n] += np.uint32(p["recv_byte0"])
+
+
+class CommTransport(Transport):
+    """The communicator's own sr_transport (sr_comm_transport) bound to a router's stream, as a Python
+    Transport: every method calls the C structure's function pointer and raises SrError on a negative
+    errno. For exchange_run / Router.regroup_run / Router.exchange_dead_run on a communicator, and for
+    sends and receives of the caller's own (device addresses, tags 0..2) between group_start and
+    group_end. Call bind() again after Router.set_stream."""
+
+    def __init__(self, comm: "Comm", router: "Router"):
+        self.comm, self.router = comm, router
+        self._t = SrTransport()
+        self.bind()
+
+    def bind(self) -> None:
+        _check(lib().sr_comm_transport(self.comm.handle, self.router.handle, ctypes.byref(self._t)),
+               "sr_comm_transport")
+
+    def group_start(self) -> None:
+        _check(self._t.group_start(self._t.user), "transport group_start")
+
+    def group_end(self) -> None:
+        _check(self._t.group_end(self._t.user), "transport group_end")
+
+    def send(self, addr: int, nbytes: int, peer: int, tag: int) -> None:
+        _check(self._t.send(self._t.user, addr, nbytes, peer, tag), "transport send")
+
+    def recv(self, addr: int, nbytes: int, peer: int, tag: int) -> None:
+        _check(self._t.recv(self._t.user, addr, nbytes, peer, tag), "transport recv")
+
+    def copy(self, dst: int, src: int, nbytes: int) -> None:
+        _check(self._t.copy(self._t.user, dst, src, nbytes), "transport copy")
+
+    def rebase(self, recs_addr: int, peers: np.ndarray, n_lines: int) -> None:
+        p = np.ascontiguousarray(peers, dtype=PEER_DTYPE)
+        _check(self._t.rebase(self._t.user, recs_addr, ctypes.cast(p.ctypes.data, ctypes.POINTER(SrExchangePeer)),
+                              int(p.size), int(n_lines)), "transport rebase")
+
+    def sizes(self, d_owner_counts: int, d_recv_counts: int):
+        return self.router.exchange_sizes(self.comm, d_owner_counts, d_recv_counts)
 
 
 def host_records(addr: int, n: int) -> np.ndarray:

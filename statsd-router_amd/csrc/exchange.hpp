@@ -11,7 +11,9 @@
 //          rebase of the received records' offsets into the receive buffer (source p's bytes land
 //          after those of sources 0 .. p-1, so its offsets move by their total).
 // RCCL is opened with dlopen at sr_comm_open: libsr_route.so does not depend on it otherwise, and a
-// process that already holds RCCL (e.g. PyTorch's) shares that copy.
+// process that already holds RCCL (e.g. PyTorch's) shares that copy. The entry points used here are one
+// instance of the communicator's collective table (sr_route.hip: CommBackend); the other is the
+// in-process backend for ranks that are threads of one process (local_board.hpp, local_comm.hpp).
 #pragma once
 
 #include <dlfcn.h>

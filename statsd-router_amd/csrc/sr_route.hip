@@ -12,10 +12,12 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <chrono>
 #include <new>
 
 #include "../../include/sr_route.h"
 #include "exchange.hpp"
+#include "local_comm.hpp"
 #include "mtu_kernel.hpp"
 #include "owner_kernel.hpp"
 #include "payload_kernel.hpp"
@@ -1183,14 +1185,141 @@ int sr_route_batch(sr_ctx *c, const uint8_t *bytes, size_t nbytes, sr_record *ou
 
 }  // extern "C"
 
-// ---- multi-GPU exchange (exchange.hpp) ----------------------------------------------------------
-struct sr_comm {
-    void *nccl;
-    int world, rank, device;
-    uint64_t *h_sizes;   // pinned, mapped, coherent: [2][world][2] sent, received, then the sequence word
-    uint64_t *d_sizes;   // its device address (nullptr: copies and a stream synchronisation instead)
-    uint64_t seq;
+// ---- multi-GPU exchange (exchange.hpp, local_comm.hpp) -------------------------------------------
+// A communicator is a small table of collectives behind one handle: the RCCL entry points are one
+// instance (sr_comm_open), the in-process board the other (sr_comm_open_local). Everything above the
+// table (the sizes publish and spin, exchange_run, regroup_run, exchange_dead_rows, the own-chunk-in-
+// place test) is one code path for both.
+struct CommBackend {
+    int (*all_to_all)(sr_comm *c, const uint64_t *send, uint64_t *recv, size_t count, hipStream_t stream);
+    int (*send)(sr_comm *c, const void *buf, size_t bytes, int peer, int tag, hipStream_t stream);
+    int (*recv)(sr_comm *c, void *buf, size_t bytes, int peer, int tag, hipStream_t stream);
+    int (*group_start)(sr_comm *c, hipStream_t stream);
+    int (*group_end)(sr_comm *c, hipStream_t stream);
+    void (*close)(sr_comm *c);
 };
+
+// what the communicator's sr_transport callbacks get (sr_comm_transport: owned by the comm)
+struct CommTransport {
+    sr_comm *comm;
+    hipStream_t stream;
+    sr_ctx *ctx;
+};
+
+struct sr_comm_group : LocalGroup {
+    using LocalGroup::LocalGroup;
+};
+
+struct sr_comm {
+    const CommBackend *be = nullptr;
+    RcclApi *r = nullptr;   // RCCL backend
+    void *nccl = nullptr;
+    LocalComm local;        // in-process backend
+    int world = 0, rank = 0, device = 0;
+    uint64_t *h_sizes = nullptr;   // pinned, mapped, coherent: [2][world][2] sent, received, then the sequence word
+    uint64_t *d_sizes = nullptr;   // its device address (nullptr: copies and a stream synchronisation instead)
+    uint64_t seq = 0;
+    uint32_t timeout_ms = 0;       // sr_comm_set_timeout: 0 = no deadline
+    int broken = 0;                // a deadline ran out on this comm
+    CommTransport tuser{};         // sr_comm_transport's `user`
+};
+
+// -EPIPE once a deadline ran out on the comm or its group broke
+static int comm_usable(sr_comm *c) {
+    if (c->broken || (c->local.group && c->local.group->board.broken())) return -EPIPE;
+    return 0;
+}
+static void comm_break(sr_comm *c) {
+    c->broken = 1;
+    if (c->local.group) c->local.group->board.break_all();
+}
+
+// RCCL
+static int rccl_be_all_to_all(sr_comm *c, const uint64_t *send, uint64_t *recv, size_t count, hipStream_t s) {
+    return c->r->all_to_all(send, recv, count, kNcclUint64, c->nccl, s) == 0 ? 0 : -EIO;
+}
+static int rccl_be_send(sr_comm *c, const void *buf, size_t bytes, int peer, int, hipStream_t s) {
+    return c->r->send(buf, bytes, kNcclUint8, peer, c->nccl, s) == 0 ? 0 : -EIO;
+}
+static int rccl_be_recv(sr_comm *c, void *buf, size_t bytes, int peer, int, hipStream_t s) {
+    return c->r->recv(buf, bytes, kNcclUint8, peer, c->nccl, s) == 0 ? 0 : -EIO;
+}
+static int rccl_be_group_start(sr_comm *c, hipStream_t) { return c->r->group_start() == 0 ? 0 : -EIO; }
+static int rccl_be_group_end(sr_comm *c, hipStream_t) { return c->r->group_end() == 0 ? 0 : -EIO; }
+static void rccl_be_close(sr_comm *c) {
+    if (c->nccl) (void)c->r->comm_destroy(c->nccl);
+}
+static const CommBackend kRcclBackend{rccl_be_all_to_all, rccl_be_send,      rccl_be_recv,
+                                      rccl_be_group_start, rccl_be_group_end, rccl_be_close};
+
+// In process: the operations of a group are collected and run on the board at group_end, on the calling
+// rank's thread and stream (local_board.hpp: run_group).
+static int local_be_run(sr_comm *c, const BoardSeg *own, size_t n_own, hipStream_t s) {
+    LocalDev dev{&c->local, s};
+    const int rc = c->local.group->board.run_group(c->rank, c->local.ops, own, n_own, dev, c->timeout_ms);
+    c->local.ops.clear();
+    if (rc == -ETIMEDOUT) c->broken = 1;
+    return rc;
+}
+static int local_be_group_start(sr_comm *c, hipStream_t s) {
+    if (c->local.in_group) return -EINVAL;
+    int rc = comm_usable(c);
+    if (!rc) rc = local_stream_ok(s);
+    if (rc) return rc;
+    c->local.ops.clear();
+    c->local.in_group = true;
+    return 0;
+}
+static int local_be_post(sr_comm *c, bool is_send, void *buf, size_t bytes, int peer, int tag) {
+    if (!c->local.in_group || !buf || peer < 0 || peer >= c->world || peer == c->rank || tag < 0 ||
+        tag >= kBoardA2ATag)
+        return -EINVAL;
+    if (bytes) c->local.ops.push_back(BoardOp{is_send, peer, tag, buf, bytes});
+    return 0;
+}
+static int local_be_send(sr_comm *c, const void *buf, size_t bytes, int peer, int tag, hipStream_t) {
+    return local_be_post(c, true, const_cast<void *>(buf), bytes, peer, tag);
+}
+static int local_be_recv(sr_comm *c, void *buf, size_t bytes, int peer, int tag, hipStream_t) {
+    return local_be_post(c, false, buf, bytes, peer, tag);
+}
+static int local_be_group_end(sr_comm *c, hipStream_t s) {
+    if (!c->local.in_group) return -EINVAL;
+    c->local.in_group = false;
+    return local_be_run(c, nullptr, 0, s);
+}
+// count elements per peer: world - 1 sends, world - 1 receives, the own element one more segment of the pull
+static int local_be_all_to_all(sr_comm *c, const uint64_t *send, uint64_t *recv, size_t count, hipStream_t s) {
+    if (c->local.in_group || !send || !recv || !count) return -EINVAL;
+    int rc = comm_usable(c);
+    if (!rc) rc = local_stream_ok(s);
+    if (rc) return rc;
+    const size_t bytes = count * sizeof(uint64_t);
+    c->local.ops.clear();
+    for (int q = 0; q < c->world; ++q) {
+        if (q == c->rank) continue;
+        c->local.ops.push_back(BoardOp{true, q, kBoardA2ATag, const_cast<uint64_t *>(send) + (size_t)q * count, bytes});
+        c->local.ops.push_back(BoardOp{false, q, kBoardA2ATag, recv + (size_t)q * count, bytes});
+    }
+    const BoardSeg own{send + (size_t)c->rank * count, recv + (size_t)c->rank * count, bytes};
+    return local_be_run(c, &own, 1, s);
+}
+static void local_be_close(sr_comm *c) {
+    local_events_retire(c->local);
+    c->local.group->board.release_rank(c->rank);
+}
+static const CommBackend kLocalBackend{local_be_all_to_all, local_be_send,      local_be_recv,
+                                       local_be_group_start, local_be_group_end, local_be_close};
+
+// the sizes' page-locked landing place (both backends)
+static int comm_sizes_alloc(sr_comm *c) {
+    if (hipHostMalloc((void **)&c->h_sizes, (4 * (size_t)c->world + 1) * sizeof(uint64_t),
+                      hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
+        return -ENOMEM;
+    memset(c->h_sizes, 0, (4 * (size_t)c->world + 1) * sizeof(uint64_t));
+    if (hipHostGetDevicePointer((void **)&c->d_sizes, c->h_sizes, 0) != hipSuccess) c->d_sizes = nullptr;
+    return 0;
+}
 
 extern "C" {
 
@@ -1207,15 +1336,13 @@ int sr_comm_open(sr_comm **out, const uint8_t id[SR_COMM_ID_BYTES], int world, i
     RcclApi *r = rccl_api();
     if (!r) return -ENOSYS;
     if (hipSetDevice(device) != hipSuccess) return -ENODEV;
-    sr_comm *c = new (std::nothrow) sr_comm{nullptr, world, rank, device, nullptr, nullptr, 0};
+    sr_comm *c = new (std::nothrow) sr_comm;
     if (!c) return -ENOMEM;
-    if (hipHostMalloc((void **)&c->h_sizes, (4 * (size_t)world + 1) * sizeof(uint64_t),
-                      hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+    c->be = &kRcclBackend, c->r = r, c->world = world, c->rank = rank, c->device = device;
+    if (comm_sizes_alloc(c)) {
         delete c;
         return -ENOMEM;
     }
-    memset(c->h_sizes, 0, (4 * (size_t)world + 1) * sizeof(uint64_t));
-    if (hipHostGetDevicePointer((void **)&c->d_sizes, c->h_sizes, 0) != hipSuccess) c->d_sizes = nullptr;
     CommId cid;
     memcpy(cid.b, id, sizeof(cid.b));
     if (((InitRankFn)r->comm_init_rank)(&c->nccl, world, cid, rank) != 0) {
@@ -1227,27 +1354,97 @@ int sr_comm_open(sr_comm **out, const uint8_t id[SR_COMM_ID_BYTES], int world, i
     return 0;
 }
 
+int sr_comm_group_open(sr_comm_group **g, int world) {
+    if (!g) return -EINVAL;
+    *g = nullptr;
+    if (world < 1 || world > (int)kMaxOwners) return -EINVAL;
+    *g = new (std::nothrow) sr_comm_group(world);
+    return *g ? 0 : -ENOMEM;
+}
+
+int sr_comm_group_close(sr_comm_group *g) {
+    if (!g) return -EINVAL;
+    if (g->board.open_ranks() > 0) return -EBUSY;
+    for (hipEvent_t e : g->retired) (void)hipEventDestroy(e);
+    delete g;
+    return 0;
+}
+
+int sr_comm_open_local(sr_comm **out, sr_comm_group *g, int rank, int device) {
+    if (!out) return -EINVAL;
+    *out = nullptr;
+    if (!g || rank < 0 || rank >= g->board.world()) return -EINVAL;
+    if (device < 0 || hipSetDevice(device) != hipSuccess) return -ENODEV;
+    sr_comm *c = new (std::nothrow) sr_comm;
+    if (!c) return -ENOMEM;
+    c->be = &kLocalBackend, c->world = g->board.world(), c->rank = rank, c->device = device;
+    int rc = g->board.take_rank(rank, device);
+    if (rc) {
+        delete c;
+        return rc;
+    }
+    // Ranks on another device: the pull reads the peer's memory, so access is enabled both ways at open.
+    // The slot is taken BEFORE the peers are scanned: of two ranks that open at the same time, the one
+    // whose take_rank comes second sees the first (both run under the board's lock), so every pair on
+    // two devices is enabled before the later rank's open returns, and no message of a pair moves
+    // before both of its ranks are open.
+    // (Not run on a one-GPU machine: unverified)
+    for (int q = 0; q < g->board.world(); ++q) {
+        const int pd = g->board.device_of(q);
+        if (q == rank || pd < 0 || pd == device) continue;
+        int a = 0, b = 0;
+        if (hipDeviceCanAccessPeer(&a, device, pd) != hipSuccess || hipDeviceCanAccessPeer(&b, pd, device) != hipSuccess ||
+            !a || !b) {
+            (void)hipGetLastError();
+            g->board.release_rank(rank);
+            delete c;
+            return -ENOTSUP;
+        }
+        (void)hipDeviceEnablePeerAccess(pd, 0);   // (hipErrorPeerAccessAlreadyEnabled is fine)
+        (void)hipSetDevice(pd);
+        (void)hipDeviceEnablePeerAccess(device, 0);
+        (void)hipSetDevice(device);
+        (void)hipGetLastError();
+    }
+    c->local.group = g, c->local.rank = rank;
+    if ((rc = local_events_create(c->local)) || (rc = comm_sizes_alloc(c))) {
+        local_be_close(c);
+        delete c;
+        return rc;
+    }
+    *out = c;
+    return 0;
+}
+
+int sr_comm_set_timeout(sr_comm *c, uint32_t ms) {
+    if (!c) return -EINVAL;
+    c->timeout_ms = ms;
+    return 0;
+}
+
 void sr_comm_close(sr_comm *c) {
     if (!c) return;
-    RcclApi *r = rccl_api();
-    if (r && c->nccl) (void)r->comm_destroy(c->nccl);
     (void)hipHostFree(c->h_sizes);
+    c->be->close(c);
     delete c;
 }
 
 int sr_exchange_sizes(sr_ctx *ctx, sr_comm *comm, const uint64_t *d_owner_counts, uint64_t *d_recv_counts,
                       uint64_t *h_sent, uint64_t *h_received) {
     if (!ctx || !comm || !d_owner_counts || !d_recv_counts || !h_sent || !h_received) return -EINVAL;
-    RcclApi *r = rccl_api();
-    if (!r) return -ENOSYS;
+    int rc = comm_usable(comm);
+    if (rc) return rc;
     (void)hipSetDevice(ctx->device);
     const size_t w2 = 2 * (size_t)comm->world;
+    // one deadline for the whole call: the board's waits inside all_to_all start their own `ms` no
+    // earlier than this, and what follows them (the spin, or the fallback's drain) ends at this one
+    const auto deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(comm->timeout_ms);
     if (comm->d_sizes) {
         // one rank: nothing to exchange (the received sizes are the sent ones, written by the publish
         // kernel); then the host spins on the sequence word, checking the stream now and then for errors
-        if (comm->world > 1 &&
-            r->all_to_all(d_owner_counts, d_recv_counts, 2, kNcclUint64, comm->nccl, ctx->stream) != 0)
-            return -EIO;
+        // and, with sr_comm_set_timeout, the clock
+        if (comm->world > 1 && (rc = comm->be->all_to_all(comm, d_owner_counts, d_recv_counts, 2, ctx->stream)))
+            return rc;
         const uint64_t seq = ++comm->seq;
         hipLaunchKernelGGL(sizes_publish_kernel, dim3(1), dim3(256), 0, ctx->stream, d_owner_counts,
                            comm->world > 1 ? d_recv_counts : nullptr, d_recv_counts, comm->d_sizes,
@@ -1262,6 +1459,10 @@ int sr_exchange_sizes(sr_ctx *ctx, sr_comm *comm, const uint64_t *d_owner_counts
                     return -EIO;
                 }
                 if (q != hipErrorNotReady) return -EIO;
+                if (comm->timeout_ms && std::chrono::steady_clock::now() >= deadline) {
+                    comm_break(comm);   // the sizes may still land later: the comm is not used again
+                    return -ETIMEDOUT;
+                }
             }
             __builtin_ia32_pause();
         }
@@ -1272,13 +1473,24 @@ int sr_exchange_sizes(sr_ctx *ctx, sr_comm *comm, const uint64_t *d_owner_counts
         }
         return 0;
     }
-    if (r->all_to_all(d_owner_counts, d_recv_counts, 2, kNcclUint64, comm->nccl, ctx->stream) != 0) return -EIO;
+    if ((rc = comm->be->all_to_all(comm, d_owner_counts, d_recv_counts, 2, ctx->stream))) return rc;
     if (hipMemcpyAsync(comm->h_sizes, d_owner_counts, w2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream) !=
             hipSuccess ||
         hipMemcpyAsync(comm->h_sizes + w2, d_recv_counts, w2 * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                       ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess)
+                       ctx->stream) != hipSuccess)
         return -EIO;
+    if (!comm->timeout_ms) {
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess) return -EIO;
+    } else {   // the same wait under the deadline
+        for (hipError_t q; (q = hipStreamQuery(ctx->stream)) != hipSuccess;) {
+            if (q != hipErrorNotReady) return -EIO;
+            if (std::chrono::steady_clock::now() >= deadline) {
+                comm_break(comm);
+                return -ETIMEDOUT;
+            }
+            std::this_thread::yield();
+        }
+    }
     memcpy(h_sent, comm->h_sizes, w2 * sizeof(uint64_t));
     memcpy(h_received, comm->h_sizes + w2, w2 * sizeof(uint64_t));
     return 0;
@@ -1295,42 +1507,51 @@ static int rebase_launch(hipStream_t stream, sr_record *d_recs, const sr_exchang
     return 0;
 }
 
-// The RCCL transport of sr_exchange_data: every call enqueued on the context's stream. Both chunk
+// The communicator as an sr_transport: every call on the backend with the context's stream. Both chunk
 // kinds travel as bytes (the record chunk is 8 bytes per line on both sides of a pair).
-struct RcclTransport {
-    RcclApi *r;
-    sr_comm *comm;
-    hipStream_t stream;
-    sr_ctx *ctx;
-};
-
-static int rccl_group_start(void *u) { return ((RcclTransport *)u)->r->group_start() == 0 ? 0 : -EIO; }
-static int rccl_group_end(void *u) { return ((RcclTransport *)u)->r->group_end() == 0 ? 0 : -EIO; }
-static int rccl_send(void *u, const void *buf, size_t bytes, int peer, int) {
-    RcclTransport *t = (RcclTransport *)u;
-    return t->r->send(buf, bytes, kNcclUint8, peer, t->comm->nccl, t->stream) == 0 ? 0 : -EIO;
+static int comm_group_start(void *u) {
+    CommTransport *t = (CommTransport *)u;
+    return t->comm->be->group_start(t->comm, t->stream);
 }
-static int rccl_recv(void *u, void *buf, size_t bytes, int peer, int) {
-    RcclTransport *t = (RcclTransport *)u;
-    return t->r->recv(buf, bytes, kNcclUint8, peer, t->comm->nccl, t->stream) == 0 ? 0 : -EIO;
+static int comm_group_end(void *u) {
+    CommTransport *t = (CommTransport *)u;
+    return t->comm->be->group_end(t->comm, t->stream);
 }
-static int rccl_copy(void *u, void *dst, const void *src, size_t bytes) {
-    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ((RcclTransport *)u)->stream) == hipSuccess
+static int comm_send(void *u, const void *buf, size_t bytes, int peer, int tag) {
+    CommTransport *t = (CommTransport *)u;
+    return t->comm->be->send(t->comm, buf, bytes, peer, tag, t->stream);
+}
+static int comm_recv(void *u, void *buf, size_t bytes, int peer, int tag) {
+    CommTransport *t = (CommTransport *)u;
+    return t->comm->be->recv(t->comm, buf, bytes, peer, tag, t->stream);
+}
+static int comm_copy(void *u, void *dst, const void *src, size_t bytes) {
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ((CommTransport *)u)->stream) == hipSuccess
                ? 0 : -EIO;
 }
-static int rccl_rebase(void *u, sr_record *recs, const sr_exchange_peer *peers, int world, uint64_t) {
-    return rebase_launch(((RcclTransport *)u)->stream, recs, peers, world);
+static int comm_rebase(void *u, sr_record *recs, const sr_exchange_peer *peers, int world, uint64_t) {
+    return rebase_launch(((CommTransport *)u)->stream, recs, peers, world);
+}
+static sr_transport comm_transport(CommTransport *user) {
+    return sr_transport{user, comm_group_start, comm_group_end, comm_send, comm_recv, comm_copy, comm_rebase};
+}
+
+int sr_comm_transport(sr_comm *comm, sr_ctx *ctx, sr_transport *out) {
+    if (!comm || !ctx || !out) return -EINVAL;
+    comm->tuser = CommTransport{comm, ctx->stream, ctx};
+    *out = comm_transport(&comm->tuser);
+    return 0;
 }
 
 int sr_exchange_data(sr_ctx *ctx, sr_comm *comm, const uint8_t *d_packed, const sr_record *d_packed_recs,
                      const uint64_t *h_sent, const uint64_t *h_received, uint8_t *d_recv_bytes,
                      sr_record *d_recv_recs) {
     if (!ctx || !comm || !h_sent || !h_received) return -EINVAL;
-    RcclApi *r = rccl_api();
-    if (!r) return -ENOSYS;
+    const int usable = comm_usable(comm);
+    if (usable) return usable;
     (void)hipSetDevice(ctx->device);
-    RcclTransport rt{r, comm, ctx->stream, ctx};
-    const sr_transport t{&rt, rccl_group_start, rccl_group_end, rccl_send, rccl_recv, rccl_copy, rccl_rebase};
+    CommTransport ct{comm, ctx->stream, ctx};
+    const sr_transport t = comm_transport(&ct);
     // the own chunk already in its place (sr_pack_owner_scatter into these receive buffers): no copy
     bool in_place = false;
     if (ctx->own_set && ctx->own == comm->rank) {
@@ -1349,7 +1570,7 @@ int sr_exchange_data(sr_ctx *ctx, sr_comm *comm, const uint8_t *d_packed, const 
 // One route launch's regroup on any transport (sr_regroup_run): the split sizes, the size exchange
 // (the one host round trip), the plan, the scatter with the rank's own chunk written straight into its
 // place in the receive buffers, then the exchange without the own chunk's copy and the rebase.
-// sr_regroup_launch is this on RCCL: both run this one sequence.
+// sr_regroup_launch is this on a communicator (RCCL or in process): all run this one sequence.
 static int regroup_run(sr_ctx *ctx, const sr_transport &t, sr_sizes_fn sizes, int world, int rank,
                        const sr_batch *batches, size_t count, uint64_t *d_owner_counts, uint64_t *d_recv_counts,
                        uint8_t *d_packed, size_t packed_cap, sr_record *d_packed_recs, uint8_t *d_recv_bytes,
@@ -1374,9 +1595,9 @@ static int regroup_run(sr_ctx *ctx, const sr_transport &t, sr_sizes_fn sizes, in
                         true);
 }
 
-static int rccl_sizes(void *u, const uint64_t *d_owner_counts, uint64_t *d_recv_counts, uint64_t *h_sent,
+static int comm_sizes(void *u, const uint64_t *d_owner_counts, uint64_t *d_recv_counts, uint64_t *h_sent,
                       uint64_t *h_received) {
-    RcclTransport *t = (RcclTransport *)u;
+    CommTransport *t = (CommTransport *)u;
     return sr_exchange_sizes(t->ctx, t->comm, d_owner_counts, d_recv_counts, h_sent, h_received);
 }
 
@@ -1385,12 +1606,12 @@ int sr_regroup_launch(sr_ctx *ctx, sr_comm *comm, const sr_batch *batches, size_
                       sr_record *d_packed_recs, uint8_t *d_recv_bytes, size_t recv_bytes_cap,
                       sr_record *d_recv_recs, size_t recv_recs_cap, uint64_t *h_sent, uint64_t *h_received) {
     if (!ctx || !comm) return -EINVAL;
-    RcclApi *r = rccl_api();
-    if (!r) return -ENOSYS;
+    const int usable = comm_usable(comm);
+    if (usable) return usable;
     (void)hipSetDevice(ctx->device);
-    RcclTransport rt{r, comm, ctx->stream, ctx};
-    const sr_transport t{&rt, rccl_group_start, rccl_group_end, rccl_send, rccl_recv, rccl_copy, rccl_rebase};
-    return regroup_run(ctx, t, rccl_sizes, comm->world, comm->rank, batches, count, d_owner_counts, d_recv_counts,
+    CommTransport ct{comm, ctx->stream, ctx};
+    const sr_transport t = comm_transport(&ct);
+    return regroup_run(ctx, t, comm_sizes, comm->world, comm->rank, batches, count, d_owner_counts, d_recv_counts,
                        d_packed, packed_cap, d_packed_recs, d_recv_bytes, recv_bytes_cap, d_recv_recs, recv_recs_cap,
                        h_sent, h_received);
 }
@@ -1464,10 +1685,10 @@ int sr_exchange_dead_run(sr_ctx *ctx, const sr_transport *t, int world, int rank
 
 int sr_exchange_dead(sr_ctx *ctx, sr_comm *comm, const sr_batch *batches, size_t count, uint64_t *d_all_dead) {
     if (!comm || !exchange_dead_args_ok(ctx, comm->world, comm->rank, batches, count, d_all_dead)) return -EINVAL;
-    RcclApi *r = rccl_api();
-    if (!r) return -ENOSYS;
-    RcclTransport rt{r, comm, ctx->stream, ctx};
-    const sr_transport t{&rt, rccl_group_start, rccl_group_end, rccl_send, rccl_recv, rccl_copy, rccl_rebase};
+    const int usable = comm_usable(comm);
+    if (usable) return usable;
+    CommTransport ct{comm, ctx->stream, ctx};
+    const sr_transport t = comm_transport(&ct);
     return exchange_dead_impl(ctx, t, comm->world, comm->rank, batches, count, d_all_dead);
 }
 

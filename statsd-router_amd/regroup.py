@@ -218,8 +218,10 @@ class LaunchRegrouper:
 
     def __init__(self, pkg, router, max_total_bytes: int, max_total_records: int, group=None, comm=None,
                  own_in_place: bool = True, one_call: bool = True):
-        """comm: a pkg.Comm for the C-ABI exchange (sr_exchange_sizes / sr_exchange_data over RCCL);
-        None: torch.distributed collectives on `group` (gloo in the CPU tests, nccl on GPUs).
+        """comm: a pkg.Comm for the C-ABI exchange (sr_exchange_sizes / sr_exchange_data over RCCL, or
+        between the threads of one process with pkg.Comm.local; the ranks are the comm's, torch.distributed
+        need not be initialised); None: torch.distributed collectives on `group` (gloo in the CPU tests,
+        nccl on GPUs).
         own_in_place (C-ABI exchange): the pack writes the rank's own chunk straight into the receive
         buffers; False: one sr_pack_many_by_owner and a device copy of the own chunk (A/B runs).
         one_call (with own_in_place): the whole regroup in one sr_regroup_launch; False: the same work in
@@ -227,7 +229,7 @@ class LaunchRegrouper:
         self.pkg, self.router, self.group, self.comm = pkg, router, group, comm
         self.own_in_place = own_in_place
         self.one_call = one_call
-        self.G = dist.get_world_size(group)
+        self.G = comm.world if comm is not None else dist.get_world_size(group)
         if not 1 <= self.G <= pkg.SR_MAX_OWNERS:
             raise ValueError(f"regroup over {self.G} ranks: at most {pkg.SR_MAX_OWNERS}")
         dev = torch.device("cuda", router.device)
