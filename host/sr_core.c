@@ -16,6 +16,7 @@
  * There is no CPU routing path: the shard of every line, data or ping, comes from the GPU.
  */
 #include "../include/sr_router.h"
+#include "sr_slots.h"
 
 #include <errno.h>
 #include <stdarg.h>
@@ -55,6 +56,10 @@ struct sr_core {
     int trace;                               /* log_level TRACE: per-line hashes from the GPU     */
     uint32_t *dg_ends[2];                    /* TRACE: datagram ends of the batch in each slot    */
     size_t dg_n[2], dg_cap[2];
+    /* sr_core_submit_slots: the batch in a slot is datagrams left in 4096-byte slots of its buffer */
+    uint16_t *slot_lens[2];                  /* their lengths as received                          */
+    uint32_t *slot_ends[2];                  /* framed end offset after each (sr_slots.h)          */
+    size_t slot_n[2];                        /* slots of the batch; 0: the buffer holds framed bytes */
     uint64_t *ping_hash;                     /* TRACE: the ping names' hashes                      */
     int payloads;                            /* sr_core_set_payloads: packets from the slot's arena */
     int host_fills;                          /* the host changed pending buffers since the last  */
@@ -139,6 +144,10 @@ void sr_core_close(sr_core *c) {
     free(c->ping_hash);
     free(c->dg_ends[0]);
     free(c->dg_ends[1]);
+    for (int k = 0; k < 2; k++) {
+        free(c->slot_lens[k]);
+        free(c->slot_ends[k]);
+    }
     free(c->alive);
     free(c->ds);
     free(c);
@@ -233,9 +242,17 @@ static void drop_probed(sr_core *c) {
         for (uint64_t m = c->probed[w]; m; m &= m - 1) c->ds[w * 64 + (uint32_t)__builtin_ctzll(m)].fill = 0;
 }
 
+/* Where framed byte `off` of the batch in `slot` lies: in the framed bytes, or, for a slot batch, in its
+ * datagram's slot (the datagram there is its framed form: sr_core_submit_slots wrote the missing '\n').
+ * A line, and a datagram, is one run of bytes either way. */
+static const uint8_t *batch_at(const sr_core *c, int slot, const uint8_t *framed, uint32_t off) {
+    if (!c->slot_n[slot]) return framed + off;
+    return sr_slot_addr(c->in[slot], SR_DATA_BUF_SIZE, c->slot_ends[slot], c->slot_n[slot], off);
+}
+
 /* The WARN line of an unrouted record, with the reference's text. */
-static void warn_line(sr_core *c, const uint8_t *framed, const sr_record *r) {
-    const char *line = (const char *)framed + r->offset;
+static void warn_line(sr_core *c, int slot, const uint8_t *framed, const sr_record *r) {
+    const char *line = (const char *)batch_at(c, slot, framed, r->offset);
     const int len = r->length;
     if (r->route == SR_ROUTE_INVALID_LENGTH) {
         /* sr-main.c:184 */
@@ -269,16 +286,21 @@ static int trace_batch(sr_core *c, int slot, const uint8_t *framed, size_t nbyte
         c->dg_n[slot] = 0;
         return rc;
     }
-    const size_t nd = c->dg_n[slot];
+    /* a slot batch brings its own boundaries: one per slot, an empty datagram repeating the one before
+     * (the reference logs nothing for it, sr-main.c:170) */
+    const size_t nd = c->slot_n[slot] ? c->slot_n[slot] : c->dg_n[slot];
+    const uint32_t *ends = c->slot_n[slot] ? c->slot_ends[slot] : c->dg_ends[slot];
     for (size_t g = 0; g <= nd; g++) {   /* the datagrams, then whatever no boundary covers */
-        const size_t end = g < nd ? c->dg_ends[slot][g] : nbytes;
-        if (g < nd)
-            core_log(c, SR_TRACE, "%s: got packet %.*s", "udp_read_cb", (int)(end - d0), (const char *)framed + d0);
+        const size_t end = g < nd ? ends[g] : nbytes;
+        if (g < nd && (end > d0 || !c->slot_n[slot]))
+            core_log(c, SR_TRACE, "%s: got packet %.*s", "udp_read_cb", (int)(end - d0),
+                     (const char *)batch_at(c, slot, framed, (uint32_t)d0));
         for (; i < n && (g == nd || rec[i].offset < end); i++) {
             if (rec[i].route == SR_ROUTE_INVALID_LENGTH || rec[i].route == SR_ROUTE_INVALID_FORMAT)
-                warn_line(c, framed, &rec[i]);
+                warn_line(c, slot, framed, &rec[i]);
             else
-                trace_line(c, (const char *)framed + rec[i].offset, rec[i].length, hs[i], rec[i].route);
+                trace_line(c, (const char *)batch_at(c, slot, framed, rec[i].offset), rec[i].length, hs[i],
+                           rec[i].route);
         }
         d0 = end;
     }
@@ -294,7 +316,7 @@ static void complete(sr_core *c, int slot, const uint8_t *framed, size_t nbytes,
     /* without the TRACE inputs (the slot was not traced) the WARN lines still come, from the sorted
      * records' unrouted tail, in input order */
     if ((!c->trace || trace_batch(c, slot, framed, nbytes) != 0) && c->log_level <= SR_WARN)
-        for (size_t i = r->n_valid; i < r->n_records; i++) warn_line(c, framed, &r->sorted[i]);
+        for (size_t i = r->n_valid; i < r->n_records; i++) warn_line(c, slot, framed, &r->sorted[i]);
     /* sr_core_set_payloads: the packets' lines laid end to end by the GPU, packet q at
      * arena[offs[q] + carry, offs[q + 1]) (the carry's room is unwritten: the host holds those bytes) */
     const uint8_t *arena = NULL;
@@ -329,7 +351,7 @@ static void complete(sr_core *c, int slot, const uint8_t *framed, size_t nbytes,
             /* the new active buffer: the carried bytes (already in place) + this batch's lines */
             uint32_t f = p->carry;
             for (uint32_t k = 0; k < p->nlines; k++) {
-                memcpy(d->pending + f, framed + rec[k].offset, rec[k].length);
+                memcpy(d->pending + f, batch_at(c, slot, framed, rec[k].offset), rec[k].length);
                 f += rec[k].length;
             }
             d->fill = f;
@@ -338,7 +360,7 @@ static void complete(sr_core *c, int slot, const uint8_t *framed, size_t nbytes,
         int iv = 0;
         if (p->carry) c->iov[iv++] = (struct iovec){d->pending, p->carry};
         for (uint32_t k = 0; k < p->nlines; k++)
-            c->iov[iv++] = (struct iovec){(void *)(framed + rec[k].offset), rec[k].length};
+            c->iov[iv++] = (struct iovec){(void *)batch_at(c, slot, framed, rec[k].offset), rec[k].length};
         const uint32_t bytes = (uint32_t)p->carry + p->length;
         d->packets += 1;
         d->traffic = (int32_t)((uint32_t)d->traffic + bytes);
@@ -355,7 +377,9 @@ static int submit(sr_core *c, int slot, const uint8_t *framed, size_t nbytes) {
         for (uint32_t s = 0; s < c->n; s++) c->fill16[s] = (uint16_t)c->ds[s].fill;
         fill = c->fill16;
     }
-    int rc = sr_route_pack_submit(c->ctx, slot, framed, nbytes, fill);
+    int rc = c->slot_n[slot] ? sr_route_pack_submit_slots(c->ctx, slot, c->in[slot], SR_DATA_BUF_SIZE, c->slot_lens[slot],
+                                                          c->slot_n[slot], fill)
+                             : sr_route_pack_submit(c->ctx, slot, framed, nbytes, fill);
     if (rc) return rc;
     c->host_fills = 0;
     return 0;
@@ -398,15 +422,13 @@ static int note_datagrams(sr_core *c, int slot, const uint32_t *ends, size_t n) 
     return 0;
 }
 
-int sr_core_submit_datagrams(sr_core *c, int slot, size_t nbytes, const uint32_t *ends, size_t n_datagrams) {
-    if (!c || slot < 0 || slot > 1 || nbytes > c->max_batch) return -EINVAL;
-    if (c->in_flight == slot) return -EBUSY;
-    if (nbytes == 0) return 0;
-    if (c->fail_submit && ++c->submits == c->fail_submit) return -EIO;   /* as a failed sr_route_pack_submit */
-    int rc = note_datagrams(c, slot, ends, n_datagrams);
-    if (rc) return rc;
+/* Start the batch prepared in `slot` (framed bytes, or slots when slot_n[slot] != 0) and complete the other
+ * slot's batch: the common half of sr_core_submit_datagrams and sr_core_submit_slots. */
+static int submit_slot(sr_core *c, int slot, size_t nbytes) {
+    int rc;
     if ((rc = submit(c, slot, c->in[slot], nbytes))) {
         c->dg_n[slot] = 0;
+        c->slot_n[slot] = 0;
         return rc;   /* nothing submitted: sr_core_in_flight() is not `slot` */
     }
     const int prev = c->in_flight;
@@ -427,8 +449,59 @@ int sr_core_submit_datagrams(sr_core *c, int slot, size_t nbytes, const uint32_t
                  strerror(-rc_back));
     c->in_flight = -1;
     if (submit(c, slot, c->in[slot], nbytes) == 0) c->in_flight = slot;   /* (its datagram ends kept) */
-    else c->dg_n[slot] = 0;
+    else c->dg_n[slot] = c->slot_n[slot] = 0;
     return rc;
+}
+
+int sr_core_submit_datagrams(sr_core *c, int slot, size_t nbytes, const uint32_t *ends, size_t n_datagrams) {
+    if (!c || slot < 0 || slot > 1 || nbytes > c->max_batch) return -EINVAL;
+    if (c->in_flight == slot) return -EBUSY;
+    if (nbytes == 0) return 0;
+    if (c->fail_submit && ++c->submits == c->fail_submit) return -EIO;   /* as a failed sr_route_pack_submit */
+    c->slot_n[slot] = 0;
+    int rc = note_datagrams(c, slot, ends, n_datagrams);
+    if (rc) return rc;
+    return submit_slot(c, slot, nbytes);
+}
+
+int sr_core_submit_slots(sr_core *c, int slot, const uint16_t *lens, size_t n_slots) {
+    if (!c || slot < 0 || slot > 1 || (n_slots && !lens)) return -EINVAL;
+    const size_t room = c->max_batch / SR_DATA_BUF_SIZE;
+    if (n_slots > room || n_slots > SR_MAX_SLOTS) return -EINVAL;
+    if (c->in_flight == slot) return -EBUSY;
+    if (!c->slot_lens[slot]) {   /* once per slot, for the whole arena */
+        uint16_t *l = malloc((room ? room : 1) * sizeof(uint16_t));
+        uint32_t *e = malloc((room ? room : 1) * sizeof(uint32_t));
+        if (!l || !e) {
+            free(l);
+            free(e);
+            return -ENOMEM;
+        }
+        c->slot_lens[slot] = l;
+        c->slot_ends[slot] = e;
+    }
+    /* udp_read_cb's framing in place (sr-main.c:163-173): the cap, and the missing '\n' written behind the
+     * datagram, so that the slot holds its framed form for the host's own reads; the device frames the same
+     * bytes from the lengths as received */
+    uint32_t pos = 0;
+    for (size_t j = 0; j < n_slots; j++) {
+        uint8_t *d = c->in[slot] + j * SR_DATA_BUF_SIZE;
+        const uint32_t n = lens[j] < SR_MAX_DATAGRAM ? lens[j] : SR_MAX_DATAGRAM;
+        if (n) {
+            pos += n;
+            if (d[n - 1] != '\n') {
+                d[n] = '\n';
+                pos += 1;
+            }
+        }
+        c->slot_lens[slot][j] = lens[j];
+        c->slot_ends[slot][j] = pos;
+    }
+    if (pos == 0) return 0;
+    if (c->fail_submit && ++c->submits == c->fail_submit) return -EIO;   /* as a failed sr_route_pack_submit */
+    c->dg_n[slot] = 0;
+    c->slot_n[slot] = n_slots;
+    return submit_slot(c, slot, pos);
 }
 
 int sr_core_submit(sr_core *c, int slot, size_t nbytes) { return sr_core_submit_datagrams(c, slot, nbytes, NULL, 0); }
@@ -441,6 +514,7 @@ int sr_core_route_datagrams(sr_core *c, const uint8_t *framed, size_t nbytes, co
     int rc = sr_core_drain(c);
     if (rc) return rc;
     if (nbytes == 0) return 0;
+    c->slot_n[0] = 0;
     if ((rc = note_datagrams(c, 0, ends, n_datagrams))) return rc;
     if ((rc = submit(c, 0, framed, nbytes))) {
         c->dg_n[0] = 0;

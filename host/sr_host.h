@@ -56,6 +56,8 @@ typedef struct sr_config {
     int require_gpu;                            /* a data thread without a GPU ends the process */
     int dt_sync;                                /* SR_DT_SYNC=1: every read event routes and completes its */
                                                 /* batch before returning (no double buffering; A/B)    */
+    int dt_device_framing;                      /* SR_DEVICE_FRAMING=1: datagrams stay in their recvmmsg slots and */
+                                                /* are framed on the GPU (sr_core_submit_slots); off by default    */
     int dt_yield;                               /* full batches per read event before timers run (0: no cap) */
     double dt_yield_s;                          /* seconds per read event before timers run (0: no cap)  */
     /* alive bits published by the health checker to the data threads */

@@ -46,6 +46,9 @@ typedef struct data_thread {
     int slot;
     struct mmsghdr rmsg[RECV_VLEN];
     struct iovec riov[RECV_VLEN];
+    /* SR_DEVICE_FRAMING=1: the batch is an arena of cap / 4096 slots; datagram j stays in slot j */
+    uint16_t *slens;         /* the received lengths, one per slot */
+    size_t nslots;           /* slots of the arena in use */
     /* log_level TRACE: the framed datagrams' end offsets in the batch (sr_core_submit_datagrams) */
     int trace;
     uint32_t *ends;
@@ -123,9 +126,17 @@ static void refresh_alive(data_thread *d) {
  * ends with its batch in flight: the next read event completes it, or, when the loop finds nothing
  * else to do, the idle watcher does, so a lone datagram still costs about one GPU round trip. */
 static void submit_batch(data_thread *d) {
-    if (!d->len) return;
-    refresh_alive(d);
-    int rc = sr_core_submit_datagrams(d->core, d->slot, d->len, d->ends, d->nends);
+    int rc;
+    if (d->c->dt_device_framing) {
+        if (!d->nslots) return;
+        refresh_alive(d);
+        rc = sr_core_submit_slots(d->core, d->slot, d->slens, d->nslots);
+        d->nslots = 0;
+    } else {
+        if (!d->len) return;
+        refresh_alive(d);
+        rc = sr_core_submit_datagrams(d->core, d->slot, d->len, d->ends, d->nends);
+    }
     if (rc) sr_log(SR_ERROR, "%s: sr_core_submit() failed %s", "udp_read_cb", strerror(-rc));
     d->len = 0;
     d->nends = 0;
@@ -171,6 +182,34 @@ static void udp_read_cb(struct ev_loop *loop, ev_io *w, int revents) {
     int batches = 0;
     const ev_tstamp t0 = d->c->dt_yield_s > 0 ? ev_time() : 0;
     for (;;) {
+        if (d->c->dt_device_framing) {
+            /* datagrams stay where recvmmsg puts them, one per 4096-byte slot of the arena, and are
+             * framed on the GPU: no byte is moved here. The batch is full when fewer than RECV_VLEN slots
+             * are free. */
+            const size_t slots = d->cap / SR_DATA_BUF_SIZE < SR_MAX_SLOTS ? d->cap / SR_DATA_BUF_SIZE : SR_MAX_SLOTS;
+            if (slots - d->nslots < (size_t)RECV_VLEN) {
+                if (d->c->dt_sync) route_batch(d);
+                else submit_batch(d);
+                if (d->c->dt_yield && ++batches >= d->c->dt_yield) break;
+                if (d->c->dt_yield_s > 0 && ev_time() - t0 >= d->c->dt_yield_s) break;
+            }
+            for (int j = 0; j < RECV_VLEN; j++) {
+                d->riov[j] = (struct iovec){d->batch + (d->nslots + (size_t)j) * SR_DATA_BUF_SIZE, SR_MAX_DATAGRAM};
+                memset(&d->rmsg[j].msg_hdr, 0, sizeof(struct msghdr));
+                d->rmsg[j].msg_hdr.msg_iov = &d->riov[j];
+                d->rmsg[j].msg_hdr.msg_iovlen = 1;
+            }
+            int k = recvmmsg(d->sock_in, d->rmsg, RECV_VLEN, MSG_DONTWAIT, NULL);
+            if (k < 0) {
+                if (errno != EAGAIN && errno != EWOULDBLOCK && errno != EINTR)
+                    sr_log(SR_WARN, "%s: recv() failed %s", "udp_read_cb", strerror(errno));
+                break;
+            }
+            for (int j = 0; j < k; j++) d->slens[d->nslots + (size_t)j] = (uint16_t)d->rmsg[j].msg_len;
+            d->nslots += (size_t)k;
+            if (k < RECV_VLEN) break;   /* drained */
+            continue;
+        }
         if (d->cap - d->len < (size_t)RECV_VLEN * SR_DATA_BUF_SIZE) {
             if (d->c->dt_sync) route_batch(d);
             else submit_batch(d);
@@ -304,6 +343,10 @@ void *sr_data_thread(void *arg) {
     d->slot = 0;
     d->batch = sr_core_slot_buffer(d->core, 0, &d->cap);
     d->trace = sr_log_level <= SR_TRACE;
+    if (c->dt_device_framing && !(d->slens = calloc(d->cap / SR_DATA_BUF_SIZE + 1, sizeof(uint16_t)))) {
+        sr_log(SR_ERROR, "%s: malloc() failed %s", fn, strerror(errno));
+        return thread_fail(d, 0);
+    }
     d->nout = c->socket_out_num;
     d->sock_out = calloc((size_t)d->nout, sizeof(int));
     d->smsg = calloc((size_t)d->nout * SEND_VLEN, sizeof(struct mmsghdr));
@@ -369,6 +412,8 @@ int main(int argc, char *argv[]) {
     config.n_devices = nd ? atoi(nd) : 1;
     const char *ds = getenv("SR_DT_SYNC"), *dy = getenv("SR_DT_YIELD"), *dys = getenv("SR_DT_YIELD_S");
     config.dt_sync = ds && ds[0] == '1';
+    const char *df = getenv("SR_DEVICE_FRAMING");
+    config.dt_device_framing = df && df[0] == '1';
     config.dt_yield = dy ? atoi(dy) : 0;
     config.dt_yield_s = dys ? atof(dys) : READ_EVENT_SECONDS;
 

@@ -77,6 +77,14 @@ size_t sr_frame_datagram(uint8_t *dst, const uint8_t *src, size_t len);
 size_t sr_frame_datagrams(uint8_t *dst, size_t dst_cap, const uint8_t *const *dgrams,
                           const size_t *lens, size_t count);
 
+/* The framed size of datagrams that stay where recvmmsg left them (host only, nothing is moved):
+ * datagram j occupies bytes [j * stride, j * stride + lens[j]) of `slots`. Returns what sr_frame_datagrams
+ * would return for them, looking at one byte per datagram, and, with ends != NULL, ends[j] = the framed end
+ * offset (exclusive) after datagram j (an empty datagram repeats the previous value). A caller that frames
+ * on the device (sr_frame_slots) gets the route launch's nbytes from here. */
+size_t sr_frame_slots_size(const uint8_t *slots, size_t stride, const uint16_t *lens, size_t count,
+                           uint32_t *ends);
+
 /* ---- context -------------------------------------------------------------------------------- */
 typedef struct sr_ctx sr_ctx;
 
@@ -541,6 +549,44 @@ int sr_set_payloads(sr_ctx *ctx, int on);
 int sr_route_pack_payloads(sr_ctx *ctx, int slot, const uint8_t **payload, const uint32_t **offsets,
                            size_t *n_packets);
 
+/* ---- framing on the device: datagrams straight from their recvmmsg slots ------------------------ */
+/* recvmmsg leaves a strided array of slots and a length per slot. sr_frame_slots frames them on the device
+ * exactly as sr_frame_datagrams does on the host (udp_read_cb, sr-main.c:163-173): for each j in order the
+ * first n = min(lens[j], SR_MAX_DATAGRAM) bytes of slot j, then one '\n' when n > 0 and byte n - 1 is not
+ * one; nothing for n = 0.
+ *   d_slots / d_lens: device-readable memory (device memory, or page-locked host memory by its device
+ *                     address); datagram j at d_slots + j * stride;
+ *   d_bytes / cap   : the framed batch. Nothing at or past min(total, cap) is written;
+ *   d_ends          : NULL, or count u32: the framed end offset (exclusive) after datagram j;
+ *   d_total         : the framed bytes needed (= d_ends[count - 1]); it may exceed cap.
+ * Asynchronous on the context's stream. The first call with count > 0 allocates the context's scan scratch,
+ * once and at its full size (not inside stream capture); later calls allocate nothing and can be captured
+ * in a graph. count == 0 writes *d_total = 0 and nothing else. Returns 0, -EINVAL (a null context or
+ * required pointer, stride < SR_DATA_BUF_SIZE or > SR_MAX_SLOT_STRIDE, count > SR_MAX_SLOTS), -ENOMEM, -EIO. */
+#define SR_MAX_SLOTS 65536u
+#define SR_MAX_SLOT_STRIDE 134217728u   /* 128 MiB: offsets inside a gather run stay below 2^31 */
+typedef struct sr_slot_batch {
+    const uint8_t *d_slots; size_t stride;   /* stride >= SR_DATA_BUF_SIZE; any byte alignment */
+    const uint16_t *d_lens; size_t count;    /* count <= SR_MAX_SLOTS; values above 4095 are capped */
+    uint8_t *d_bytes; size_t cap;            /* framed batch out */
+    uint32_t *d_ends;                        /* NULL or count entries */
+    uint64_t *d_total;                       /* framed bytes needed (may exceed cap) */
+} sr_slot_batch;
+int sr_frame_slots(sr_ctx *ctx, const sr_slot_batch *b);
+
+/* sr_route_pack_submit with the framing on the device instead of a host-to-device copy of a framed batch:
+ * `slots` is page-locked host memory that the device can read (sr_alloc_host), datagram j at slots +
+ * j * stride, lens[j] bytes long. The function asks for the memory's device address and returns -EINVAL
+ * when it has none. lens is copied into the slot's staging and is free on return; the datagrams must stay
+ * unchanged until the slot's result is taken. The framed size comes from sr_frame_slots_size; -EINVAL when
+ * it exceeds max_batch_bytes; 0 (no datagrams, or only empty ones) behaves as sr_route_pack_submit(NULL, 0).
+ * The frame kernels read the slots in place and write the context's input buffer; route, packing, copy-out
+ * and the optional trace and payloads follow unchanged, and record offsets refer to the framed stream.
+ * sr_route_pack_result returns -EIO when the device's framed total differs from the host's, i.e. the
+ * caller changed the slots while the batch was in flight. Other returns as sr_route_pack_submit. */
+int sr_route_pack_submit_slots(sr_ctx *ctx, int slot, const uint8_t *slots, size_t stride,
+                               const uint16_t *lens, size_t count, const uint16_t *fill);
+
 /* ---- owner side of the multi-GPU regroup: received lines into packets ------------------------------ */
 /* After sr_regroup_launch / sr_regroup_run the lines of the shards a GPU owns lie in d_recv_bytes /
  * d_recv_recs: every source's chunk in source order 0, 1, ..., each chunk batch 0's lines, then batch
@@ -650,7 +696,8 @@ int sr_flush_pending(sr_ctx *ctx, uint16_t *d_fill, const uint8_t *d_pend, sr_pa
 int sr_set_knob(sr_ctx *ctx, int knob, int64_t value);
 
 /* Page-locked host memory for the batches and outputs of the host-memory calls (their copies then
- * run at full link rate). NULL on failure. */
+ * run at full link rate). The device can also read it in place: it is what sr_route_pack_submit_slots
+ * takes as `slots`. NULL on failure. */
 void *sr_alloc_host(size_t bytes);
 void sr_free_host(void *p);
 

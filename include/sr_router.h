@@ -98,6 +98,20 @@ int sr_core_route_datagrams(sr_core *core, const uint8_t *framed, size_t nbytes,
                             size_t n_datagrams);
 int sr_core_submit_datagrams(sr_core *core, int slot, size_t nbytes, const uint32_t *ends, size_t n_datagrams);
 
+/* sr_core_submit for datagrams that stay where recvmmsg left them: slot `slot`'s buffer
+ * (sr_core_slot_buffer) is read as an arena of capacity / SR_DATA_BUF_SIZE slots of SR_DATA_BUF_SIZE bytes,
+ * datagram j in the first lens[j] bytes of slot j (lengths above SR_MAX_DATAGRAM are capped, as recv()
+ * caps them). Nothing is moved: the datagrams are framed on the device (sr_route_pack_submit_slots). The
+ * core computes the framed ends itself and writes a missing final '\n' into the byte behind a datagram
+ * (slot j's byte lens[j], always inside the slot), so that WARN and TRACE texts, "got packet" lines, the
+ * packets' iovecs and the new pending buffers are read from the slots. lens is copied. Everything else is
+ * sr_core_submit's: the other slot's batch is completed, batches complete in submission order with the
+ * packets, counters and log lines sr_core_route would produce for the same datagrams framed, sr_core_drain,
+ * sr_core_set_payloads and the fault injection apply unchanged, and a TRACE core needs no boundaries
+ * argument (every slot is a datagram). The slot's buffer must stay unchanged until the batch completes.
+ * Returns 0, -EBUSY, -EINVAL (n_slots over the arena or SR_MAX_SLOTS), -ENOMEM or an sr_route_pack_* error. */
+int sr_core_submit_slots(sr_core *core, int slot, const uint16_t *lens, size_t n_slots);
+
 /* The core's device context (sr_route.h), e.g. for sr_set_layout or sr_set_knob (developer A/B runs).
  * Owned by the core. */
 sr_ctx *sr_core_context(sr_core *core);

@@ -57,7 +57,10 @@ ABI_FUNCTIONS = (
     "sr_pack_payloads_many", "sr_pack_payloads", "sr_set_payloads", "sr_route_pack_payloads",
     "sr_exchange_dead_run", "sr_exchange_dead", "sr_owner_pack", "sr_flush_pending",
     "sr_comm_group_open", "sr_comm_group_close", "sr_comm_open_local", "sr_comm_set_timeout", "sr_comm_transport",
+    "sr_frame_slots_size", "sr_frame_slots", "sr_route_pack_submit_slots",
 )
+SR_MAX_SLOTS = 65536
+SR_MAX_SLOT_STRIDE = 1 << 27
 SR_MAX_PACK_DOWNSTREAMS = 4096
 SR_LAYOUT_AUTO, SR_LAYOUT_UNIFORM, SR_LAYOUT_SEGMENTS, SR_LAYOUT_CHUNKS = 0, 1, 2, 3
 SR_COMM_ID_BYTES = 128
@@ -117,6 +120,12 @@ class SrPayloadBatch(ctypes.Structure):
         ("d_pend_out", ctypes.c_void_p), ("d_payload", ctypes.c_void_p), ("payload_cap", ctypes.c_size_t),
         ("d_offsets", ctypes.c_void_p), ("d_total", ctypes.c_void_p),
     ]
+
+
+class SrSlotBatch(ctypes.Structure):
+    _fields_ = [("d_slots", ctypes.c_void_p), ("stride", ctypes.c_size_t), ("d_lens", ctypes.c_void_p),
+                ("count", ctypes.c_size_t), ("d_bytes", ctypes.c_void_p), ("cap", ctypes.c_size_t),
+                ("d_ends", ctypes.c_void_p), ("d_total", ctypes.c_void_p)]
 
 
 class SrOwnerBatch(ctypes.Structure):
@@ -262,6 +271,9 @@ def _load_route_lib() -> ctypes.CDLL:
         "sr_exchange_dead": (ctypes.c_int, [vp, vp, ctypes.POINTER(SrBatch), ctypes.c_size_t, vp]),
         "sr_owner_pack": (ctypes.c_int, [vp, ctypes.POINTER(SrOwnerBatch)]),
         "sr_flush_pending": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_size_t, vp, vp, ctypes.c_size_t, vp, vp]),
+        "sr_frame_slots_size": (ctypes.c_size_t, [vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]),
+        "sr_frame_slots": (ctypes.c_int, [vp, ctypes.POINTER(SrSlotBatch)]),
+        "sr_route_pack_submit_slots": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]),
     }
     for name in ABI_FUNCTIONS:
         if os.environ.get("SR_ROUTE_LIB") and not hasattr(lib, name):
@@ -311,6 +323,44 @@ def frame_datagrams(dgrams: Sequence[bytes]) -> bytes:
     if n == ctypes.c_size_t(-1).value:
         raise SrError(errno.ENOSPC, "sr_frame_datagrams")
     return out.raw[:n]
+
+
+def frame_slots_size(slots: np.ndarray, stride: int, lens, want_ends: bool = False):
+    """sr_frame_slots_size: the framed size of datagrams left in their slots (datagram j = lens[j] bytes at
+    slots[j * stride:]), one byte looked at per datagram. Returns the total, or (total, ends u32 [count])."""
+    buf = np.ascontiguousarray(slots, dtype=np.uint8)
+    ln = np.ascontiguousarray(lens, dtype=np.uint16)
+    if ln.size and int(ln.size - 1) * stride + min(int(ln[-1]), SR_MAX_DATAGRAM) > buf.size:
+        raise ValueError("the slots are shorter than (count - 1) * stride + the last datagram")
+    ends = np.zeros(max(ln.size, 1), dtype=np.uint32)
+    total = lib().sr_frame_slots_size(buf.ctypes.data if buf.size else None, stride, ln.ctypes.data if ln.size else None,
+                                      int(ln.size), ends.ctypes.data if want_ends else None)
+    return (int(total), ends[: ln.size]) if want_ends else int(total)
+
+
+class HostBuffer:
+    """Page-locked host memory from sr_alloc_host as a numpy uint8 array (`.array`); the device reads it in
+    place (Router.route_pack_submit_slots). Freed by close() or with the object."""
+
+    def __init__(self, nbytes: int):
+        self._lib = lib()
+        self.nbytes = int(nbytes)
+        self.addr = self._lib.sr_alloc_host(self.nbytes)
+        if not self.addr:
+            raise SrError(errno.ENOMEM, "sr_alloc_host")
+        self.array = np.frombuffer((ctypes.c_uint8 * max(self.nbytes, 1)).from_address(self.addr), dtype=np.uint8)
+
+    def close(self) -> None:
+        if self.addr:
+            self.array = None
+            self._lib.sr_free_host(ctypes.c_void_p(self.addr))
+            self.addr = 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ---- synthetic traffic ------------------------------------------------------------------------
@@ -554,6 +604,31 @@ class Router:
         self._pending[slot] = buf
         _check(self._lib.sr_route_pack_submit(self._h, slot, buf.ctypes.data if buf.size else None, int(buf.size),
                                               f.ctypes.data if f is not None else None), "sr_route_pack_submit")
+
+    def frame_slots(self, d_slots: int, stride: int, d_lens: int, count: int, d_bytes: int, cap: int,
+                    d_ends: int | None, d_total: int) -> None:
+        """sr_frame_slots with raw device pointers (0 / None = NULL): datagrams framed on the device from
+        their slots, asynchronous on the context's stream."""
+        b = SrSlotBatch(d_slots or None, stride, d_lens or None, count, d_bytes or None, cap, d_ends or None,
+                        d_total or None)
+        _check(self._lib.sr_frame_slots(self._h, ctypes.byref(b)), "sr_frame_slots")
+
+    def route_pack_submit_slots(self, slot: int, slots, stride: int, lens, fill=None) -> None:
+        """sr_route_pack_submit_slots (asynchronous): `slots` is page-locked memory (a HostBuffer, or its
+        address) holding datagram j in lens[j] bytes at j * stride; it must stay alive and unchanged until
+        route_pack_result(slot). fill as route_pack_submit."""
+        addr = slots.addr if isinstance(slots, HostBuffer) else int(slots)
+        ln = np.ascontiguousarray(lens, dtype=np.uint16)
+        f = None
+        if fill is not None:
+            f = np.zeros(max(self.n_downstreams, 1), dtype=np.uint16)
+            f[: self.n_downstreams] = np.asarray(fill, dtype=np.uint16)
+        self._pending = getattr(self, "_pending", {})
+        self._pending[slot] = slots
+        _check(self._lib.sr_route_pack_submit_slots(self._h, slot, ctypes.c_void_p(addr), stride,
+                                                    ln.ctypes.data if ln.size else None, int(ln.size),
+                                                    f.ctypes.data if f is not None else None),
+               "sr_route_pack_submit_slots")
 
     def route_pack_result(self, slot: int):
         """sr_route_pack_result: (sorted records, packets, fill after, n_valid, probed-dead shard ids),

@@ -69,6 +69,8 @@ def router_lib() -> ctypes.CDLL:
         L.sr_core_inject_faults.restype = ctypes.c_int
         L.sr_core_inject_faults.argtypes = [vp, ctypes.c_uint, ctypes.c_uint]
         L.sr_core_set_payloads.restype, L.sr_core_set_payloads.argtypes = ctypes.c_int, [vp, ctypes.c_int]
+        L.sr_core_submit_slots.restype = ctypes.c_int
+        L.sr_core_submit_slots.argtypes = [vp, ctypes.c_int, vp, ctypes.c_size_t]
         _RLIB = L
     return _RLIB
 
@@ -163,6 +165,24 @@ class Core:
         if self._L.sr_core_in_flight(self._h) == slot:
             self._slot = slot ^ 1   # taken, even when completing the previous batch failed
         _check(rc, "sr_core_submit")
+
+    def submit_slots(self, dgrams) -> None:
+        """Double-buffered, without framing on the host: every datagram goes as received into a 4096-byte slot
+        of the next slot's buffer (what recvmmsg does) and sr_core_submit_slots takes the lengths."""
+        slot = getattr(self, "_slot", 0)
+        cap = ctypes.c_size_t()
+        p = self._L.sr_core_slot_buffer(self._h, slot, ctypes.byref(cap))
+        if len(dgrams) * 4096 > cap.value:
+            raise SrError(28, "more datagrams than the core's buffer has slots")
+        lens = np.zeros(max(len(dgrams), 1), dtype=np.uint16)
+        for j, d in enumerate(dgrams):
+            d = bytes(d)[:4095]   # recv() reads at most 4095 bytes
+            ctypes.memmove(p + 4096 * j, d, len(d))
+            lens[j] = len(d)
+        rc = self._L.sr_core_submit_slots(self._h, slot, lens.ctypes.data, len(dgrams))
+        if self._L.sr_core_in_flight(self._h) == slot:
+            self._slot = slot ^ 1   # taken, even when completing the previous batch failed
+        _check(rc, "sr_core_submit_slots")
 
     def inject_faults(self, fail_submit: int = 0, fail_finish: int = 0) -> None:
         """sr_core_inject_faults (test hook)."""

@@ -17,6 +17,8 @@
 
 #include "../../include/sr_route.h"
 #include "exchange.hpp"
+#include "frame_host.hpp"
+#include "frame_kernel.hpp"
 #include "local_comm.hpp"
 #include "mtu_kernel.hpp"
 #include "owner_kernel.hpp"
@@ -67,6 +69,7 @@ struct sr_ctx {
     // sr_owner_pack: the receive buffer's line total and the pending fills after the dead-downstream drop
     uint64_t *d_owner_n;
     uint16_t *d_owner_fill;       // [nds]
+    uint32_t *d_frame;            // sr_frame_slots: kFrameMaxGroups sums | SR_MAX_SLOTS workgroup-local ends
     int trace;                    // sr_set_trace: submissions also return input-order records + hashes
     int payloads;                 // sr_set_payloads: submissions also return the packets' bytes
     // packing knobs (sr_set_knob): forced chunk lines (0: by shape), XCD-local chunks, chain walked in emit
@@ -85,7 +88,10 @@ struct sr_ctx {
         sr_record *sorted;
         sr_packet *packets;
         uint16_t *fill, *fill_in;
-        uint64_t *probed, *counts;
+        uint64_t *probed, *counts;   // counts[3]: the framed total the device found (slot submissions)
+        uint16_t *lens_in;        // sr_route_pack_submit_slots: the staged datagram lengths (SR_MAX_SLOTS)
+        int framed;               // the batch in the slot was framed on the device ...
+        uint64_t frame_bytes;     // ... and the host expects this many framed bytes
         // sr_set_trace: input-order records and per-line hashes (one more page-locked allocation)
         uint8_t *thost, *tdev;
         size_t trec_cap;
@@ -169,6 +175,11 @@ size_t sr_frame_datagrams(uint8_t *dst, size_t dst_cap, const uint8_t *const *dg
     return pos;
 }
 
+size_t sr_frame_slots_size(const uint8_t *slots, size_t stride, const uint16_t *lens, size_t count, uint32_t *ends) {
+    if (count && (!slots || !lens)) return 0;
+    return frame_slots_size(slots, stride, lens, count, ends);
+}
+
 void *sr_alloc_host(size_t bytes) {
     void *p = nullptr;
     return hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) == hipSuccess ? p : nullptr;
@@ -206,6 +217,7 @@ void sr_close(sr_ctx *c) {
     free_ptr(c->d_mcounts);
     free_ptr(c->d_owner_n);
     free_ptr(c->d_owner_fill);
+    free_ptr(c->d_frame);
     for (auto &sl : c->slot) {
         if (sl.host) (void)hipHostFree(sl.host);
         if (sl.thost) (void)hipHostFree(sl.thost);
@@ -860,6 +872,43 @@ int sr_pack_payloads_many(sr_ctx *c, const sr_payload_batch *batches, size_t cou
 
 int sr_pack_payloads(sr_ctx *c, const sr_payload_batch *batch) { return payloads_impl(c, batch, 1); }
 
+// The three framing launches on the context's stream (frame_kernel.hpp). The scratch is allocated once, at
+// its full size, by the first call: later calls allocate nothing and can be captured in a graph.
+static int frame_impl(sr_ctx *c, const sr_slot_batch *b) {
+    static_assert(SR_MAX_SLOTS == kFrameSpan * kFrameMaxGroups, "one wave scans the workgroup sums");
+    static_assert(SR_MAX_SLOT_STRIDE == kFrameMaxStride, "offsets inside a gather run");
+    static_assert((uint64_t)SR_MAX_SLOTS * (SR_MAX_DATAGRAM + 1u) <= 0xFFFFFFFFull, "framed offsets fit 32 bits");
+    if (!c || !b || !b->d_total) return -EINVAL;
+    if (b->stride < SR_DATA_BUF_SIZE || b->stride > kFrameMaxStride || b->count > SR_MAX_SLOTS) return -EINVAL;
+    if (b->count && (!b->d_slots || !b->d_lens)) return -EINVAL;
+    if (b->cap && !b->d_bytes) return -EINVAL;
+    (void)hipSetDevice(c->device);
+    if (b->count == 0) return hipMemsetAsync(b->d_total, 0, sizeof(uint64_t), c->stream) == hipSuccess ? 0 : -EIO;
+    if (!c->d_frame && hipMalloc(&c->d_frame, (kFrameMaxGroups + (size_t)SR_MAX_SLOTS) * sizeof(uint32_t)) != hipSuccess) {
+        c->d_frame = nullptr;
+        return -ENOMEM;
+    }
+    FrameArgs a;
+    a.slots = b->d_slots;
+    a.stride = b->stride;
+    a.lens = b->d_lens;
+    a.bytes = b->d_bytes;
+    a.cap = b->cap;
+    a.ends = b->d_ends;
+    a.total = b->d_total;
+    a.sums = c->d_frame;
+    a.loc = c->d_frame + kFrameMaxGroups;
+    a.count = (uint32_t)b->count;
+    const uint32_t groups = (a.count + kFrameSpan - 1u) / kFrameSpan;
+    const uint32_t per = (uint32_t)(kFrameWaves * kFrameRun);   // datagrams per gather workgroup
+    hipLaunchKernelGGL(frame_lens_kernel, dim3(groups), dim3(kFrameSpan), 0, c->stream, a);
+    hipLaunchKernelGGL(frame_scan_kernel, dim3(1), dim3(64), 0, c->stream, a);
+    hipLaunchKernelGGL(frame_gather_kernel, dim3((a.count + per - 1u) / per), dim3(kFrameBlock), 0, c->stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+int sr_frame_slots(sr_ctx *c, const sr_slot_batch *b) { return frame_impl(c, b); }
+
 static int grow(void **ptr, size_t *cap, size_t need, size_t elem) {
     if (need <= *cap) return 0;
     free_ptr(*ptr);
@@ -886,7 +935,8 @@ static int slot_reserve(sr_ctx *c, int k, size_t nbytes) {
     sl.rec_cap = sl.pk_cap = 0;
     const size_t o_pk = up256(rec * sizeof(sr_record)), o_fill = o_pk + up256(pk * sizeof(sr_packet));
     const size_t o_pr = o_fill + up256(nds * sizeof(uint16_t) + 2), o_cnt = o_pr + up256(nw * sizeof(uint64_t));
-    const size_t o_fin = o_cnt + 256, total = o_fin + up256(nds * sizeof(uint16_t) + 2);
+    const size_t o_fin = o_cnt + 256, o_lens = o_fin + up256(nds * sizeof(uint16_t) + 2);
+    const size_t total = o_lens + up256((size_t)SR_MAX_SLOTS * sizeof(uint16_t));
     void *h = nullptr;
     if (hipHostMalloc(&h, total, hipHostMallocMapped) != hipSuccess) return -ENOMEM;
     void *d = nullptr;
@@ -904,6 +954,7 @@ static int slot_reserve(sr_ctx *c, int k, size_t nbytes) {
     sl.probed = (uint64_t *)(sl.host + o_pr);
     sl.counts = (uint64_t *)(sl.host + o_cnt);
     sl.fill_in = (uint16_t *)(sl.host + o_fin);
+    sl.lens_in = (uint16_t *)(sl.host + o_lens);
     return 0;
 }
 
@@ -951,12 +1002,23 @@ static int slot_payload_reserve(sr_ctx *c, int k, size_t nbytes) {
     return 0;
 }
 
-static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, const uint16_t *fill) {
+// The datagrams of a slot submission (sr_route_pack_submit_slots): framed on the device into c->d_in.
+struct SlotSource {
+    const uint8_t *d_slots;   // the device address of the caller's page-locked slots
+    size_t stride;
+    const uint16_t *lens;
+    size_t count;
+};
+
+// src == nullptr: `bytes` is a framed batch in host memory. Otherwise nbytes is the framed size of src's
+// datagrams (sr_frame_slots_size, > 0) and `bytes` is unused.
+static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, const uint16_t *fill,
+                       const SlotSource *src = nullptr) {
     sr_ctx::Slot &sl = c->slot[k];
     if (sl.busy) return -EBUSY;
-    if ((nbytes && !bytes) || nbytes > c->ds.max_batch) return -EINVAL;
+    if ((nbytes && !bytes && !src) || nbytes > c->ds.max_batch) return -EINVAL;
     if (c->ds.nds > SR_MAX_PACK_DOWNSTREAMS) return -EINVAL;
-    if (nbytes && bytes[nbytes - 1] != '\n') return -EINVAL;
+    if (!src && nbytes && bytes[nbytes - 1] != '\n') return -EINVAL;
     (void)hipSetDevice(c->device);
     const size_t nds = c->ds.nds, nw = c->ds.nwords;
     int rc;
@@ -993,7 +1055,15 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
             return -EIO;
         if (hipMemsetAsync(c->d_mcounts, 0, 4 * sizeof(uint64_t), c->stream) != hipSuccess) return -EIO;
     } else {
-        if (hipMemcpyAsync(c->d_in, bytes, nbytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) return -EIO;
+        if (src) {   // the lengths staged like the fill; the datagrams read in place, no bulk copy
+            memcpy(sl.lens_in, src->lens, src->count * sizeof(uint16_t));
+            const sr_slot_batch fb{src->d_slots, src->stride, (const uint16_t *)(sl.dev + ((uint8_t *)sl.lens_in - sl.host)),
+                                   src->count, c->d_in, c->ds.max_batch, nullptr,
+                                   (uint64_t *)(sl.dev + ((uint8_t *)(sl.counts + 3) - sl.host))};
+            if ((rc = frame_impl(c, &fb))) return rc;
+        } else if (hipMemcpyAsync(c->d_in, bytes, nbytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+            return -EIO;
+        }
         // over 1024 shards with some dead the route kernel also writes the hashes: the probed-dead
         // replay then reads 8 bytes per line instead of re-hashing the names (probed_dead_kernel);
         // up to 1024 the probes note the dead shards themselves
@@ -1024,6 +1094,8 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
     o.h_fill = (uint16_t *)(sl.dev + ((uint8_t *)sl.fill - sl.host));
     o.h_probed = (uint64_t *)(sl.dev + ((uint8_t *)sl.probed - sl.host));
     o.h_counts = (uint64_t *)(sl.dev + ((uint8_t *)sl.counts - sl.host));
+    sl.framed = src != nullptr;
+    sl.frame_bytes = nbytes;
     sl.traced = c->trace;
     o.recs = (c->trace && nbytes) ? c->d_out : nullptr;   // input order, and the hashes (sr_route_pack_trace)
     o.hashes = (c->trace && nbytes) ? c->d_hash : nullptr;
@@ -1061,6 +1133,8 @@ static int pack_result(sr_ctx *c, int k, sr_pack_result *res) {
     res->n_records = (size_t)(nr < sl.rec_cap ? nr : sl.rec_cap);
     res->n_valid = (size_t)(nv < res->n_records ? nv : res->n_records);
     res->n_packets = (size_t)(np < sl.pk_cap ? np : sl.pk_cap);
+    // a slot submission: the device framed what the host sized, unless the datagrams changed in flight
+    if (sl.framed && sl.counts[3] != sl.frame_bytes) return -EIO;
     return (nr > sl.rec_cap || np > sl.pk_cap) ? -ENOSPC : 0;
 }
 
@@ -1090,6 +1164,25 @@ int sr_route_pack_payloads(sr_ctx *c, int slot, const uint8_t **payload, const u
 int sr_route_pack_submit(sr_ctx *c, int slot, const uint8_t *bytes, size_t nbytes, const uint16_t *fill) {
     if (!c || slot < 0 || slot > 1) return -EINVAL;
     return pack_submit(c, slot, bytes, nbytes, fill);
+}
+
+int sr_route_pack_submit_slots(sr_ctx *c, int slot, const uint8_t *slots, size_t stride, const uint16_t *lens,
+                               size_t count, const uint16_t *fill) {
+    if (!c || slot < 0 || slot > 1) return -EINVAL;
+    if (stride < SR_DATA_BUF_SIZE || stride > kFrameMaxStride || count > SR_MAX_SLOTS) return -EINVAL;
+    if (count && (!slots || !lens)) return -EINVAL;
+    if (c->slot[slot].busy) return -EBUSY;
+    const size_t nbytes = frame_slots_size(slots, stride, lens, count, nullptr);
+    if (nbytes > c->ds.max_batch) return -EINVAL;
+    if (nbytes == 0) return pack_submit(c, slot, nullptr, 0, fill);
+    (void)hipSetDevice(c->device);
+    void *d = nullptr;
+    if (hipHostGetDevicePointer(&d, (void *)slots, 0) != hipSuccess || !d) {   // not page-locked: no guess
+        (void)hipGetLastError();
+        return -EINVAL;
+    }
+    const SlotSource src{(const uint8_t *)d, stride, lens, count};
+    return pack_submit(c, slot, nullptr, nbytes, fill, &src);
 }
 
 int sr_route_pack_result(sr_ctx *c, int slot, sr_pack_result *res) {
