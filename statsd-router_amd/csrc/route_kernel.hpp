@@ -15,7 +15,7 @@
 //   * A launch routes up to 32 batches. Blocks 0 .. nb-1 are per-batch SCANNERS; every other block
 //     routes one 16 KiB TILE with 256 threads (4 waves), 64 contiguous bytes per thread, up to 7
 //     workgroups per CU (65-72 VGPRs, ~22.5 KiB of LDS); the every-shard-alive uniform variant fits 8
-//     (kOcc8: 63 VGPRs, 78 SGPRs, 20 KiB of LDS). With 8+ batches each batch's tiles and its
+//     (kOcc8: 64 VGPRs, 78 SGPRs, 20 KiB of LDS). With 8+ batches each batch's tiles and its
 //     scanner share one XCD class (blocks b and b + 8 land on the same XCD).
 //   * Tile entry: four buffer_load_dwordx4 per thread (+ 2 KiB of halo before the tile, 1.5 KiB in
 //     the kOcc8 variant) into a padded
@@ -32,7 +32,8 @@
 //     most one) is located in the halo (or in global memory for lines longer than it).
 //   * Lines, in windows of 256 tile-local lines: (end, first ':') staged in LDS, then every line
 //     hashed from the LDS image: sdbm with SDWA byte-pair products and one 64x64 multiply per 8
-//     bytes (sdbm_img), a name of n bytes being ceil(n/64) 64-byte segments combined with K^len.
+//     bytes (sdbm_img), a name of n bytes being ceil(n/64) 64-byte segments combined with K^len
+//     (kMx: on the matrix cores, sdbm_mx, over 64-byte windows that end at the name's end).
 //     Two lane layouts (identical records): KV_UNIFORM gives every line of a tile the same G lanes
 //     (from the tile's mean line length); KV_SEGMENTS gives a tile of mixed lengths one lane per
 //     segment, lines packed back to back over the lanes, a line's hash the difference of an
@@ -48,7 +49,10 @@
 //   * Every workgroup arrives on 8-way sharded counters without waiting; the last block waits for
 //     all arrivals and advances the context's epoch, so stale granules of earlier launches are never
 //     mistaken for current ones, with or without graph replay.
-// No MFMA: HBM-bound byte work on VALU + LDS.
+// Matrix cores: the every-shard-alive uniform variant (C2, C3, C4) hashes names with
+// v_mfma_i32_16x16x64_i8 (sdbm_mx: sdbm as signed-digit limb sums, two MFMAs per 16 name bytes), which
+// takes the multiply-adds out of the VALU stream the launch is bound by; every other variant keeps the
+// VALU Horner (sdbm_img). The rest is byte work on VALU + LDS.
 //
 // Variants. The kernels' template argument is a mask of the KV_* bits below (ABL_* bits join them in
 // developer builds only). All variants write identical records; the library holds 12 instantiations of
@@ -69,6 +73,11 @@
 #include <stdint.h>
 
 #include "../../include/sr_route.h"
+
+// 1: route_kernel<256, KV_UNIFORM | KV_ALIVE> hashes names on the matrix cores (sdbm_mx); 0: VALU Horner
+#ifndef SR_SDBM_MFMA
+#define SR_SDBM_MFMA 1
+#endif
 
 namespace srk {
 
@@ -765,6 +774,9 @@ __device__ __forceinline__ void mark_tile_end(const RouteParams &p, const uint32
 // (ABL_STAMPS, the diagnostic build of tools/stamps_route.hip, keeps the shape of what it stamps.)
 template <unsigned ABL>
 constexpr bool kOcc8 = (ABL & ~ABL_STAMPS) == (KV_UNIFORM | KV_ALIVE);
+// kMx: that variant hashes names on the matrix cores (sdbm_mx below; -DSR_SDBM_MFMA=0 keeps the VALU Horner)
+template <unsigned ABL>
+constexpr bool kMx = SR_SDBM_MFMA != 0 && kOcc8<ABL>;
 
 template <bool SLIM = false>
 struct SmemT {
@@ -892,6 +904,151 @@ __device__ __forceinline__ uint64_t sdbm_img(const S &sm, int a, int n, const ui
     for (; m < F; ++m) h = sdbm_dword_fast(h, p[m + 1]);
     if (rem) h = h * sm.pow_rem(rem) + sdbm_dword_fast(0, p[m + (m >= cross ? 1 : 0)] << (8 * (4 - rem)));
     return h;
+}
+
+// ---- sdbm on the matrix cores (the every-shard-alive uniform variant, kMx) --------------------
+// sdbm is a dot product: h = sum_i c_i K^(n-1-i) mod 2^64 with signed bytes and constant weights.
+// Each K^e mod 2^64 is split into eight signed 8-bit digits (balanced base 256, the carry out of
+// the top digit dropped): K^e = sum_l d(e, l) 2^(8 l). For a 64-byte window of signed bytes b_p the
+// eight limb sums S_l = sum_p b_p d(63 - p, l) are i8 x i8 -> i32 dot products (|S_l| <= 2^20), and
+// V = sum_l S_l 2^(8 l) = sum_p b_p K^(63 - p) mod 2^64.
+//
+// v_mfma_i32_16x16x64_i8 computes D[16x16] = A[16x64] B[64x16]. Lane l supplies the 16 bytes of its
+// own piece as B's column l & 15 in k-block l >> 4; A is block diagonal: row 4 q + r is non-zero only
+// in k-block q, where it holds digit r of the piece's 16 weights. D register r of lane l is row
+// 4 (l >> 4) + r, column l & 15: the limb sum r of lane l's own piece. No LDS and no cross-lane
+// traffic for the data; the scheme holds for any k order inside a lane's fragment as long as A and B
+// share it. Two MFMAs per 16-byte piece (digits 0..3 and 4..7); the four pieces of a window
+// accumulate inside the MFMA with per-piece weights K^(63 - 16 m - j), one limb combine per window.
+//
+// The tables live in the pad dwords of the LDS image rows (entry e at row e), staged at tile entry
+// from kMxTab: K^(64 i) (i < 24), K^-z (z < 16), and for each (piece m, digit half) five 16-byte A
+// fragments: digits r = 0..3 and a zero fragment for the lanes off the diagonal.
+typedef int v4i32 __attribute__((ext_vector_type(4)));
+constexpr int kMxPowRow = 0;                 // K^(64 i): low word at row 2 i, high word at 2 i + 1
+constexpr int kMxInvRow = 2 * kPowHi;        // K^-z, z < 16
+constexpr int kMxWRow = kMxInvRow + 32;      // A fragments: row kMxWRow + ((2 m + half) * 5 + class) * 4 + word
+constexpr int kMxRows = kMxWRow + 8 * 5 * 4;
+static_assert(kMxRows <= SmemT<true>::kRows && kMxRows <= kBlock, "the matrix-core tables in the pad dwords, one per thread");
+
+// digit l of v in balanced base 256 (digits in [-128, 127])
+constexpr int mx_digit(uint64_t v, int l) {
+    int d = 0;
+    for (int i = 0; i <= l; ++i) {
+        d = (int)(v & 0xFFu);
+        if (d >= 128) d -= 256;
+        v = (v - (uint64_t)(int64_t)d) >> 8;
+    }
+    return d;
+}
+struct MxTab {
+    uint32_t w[kMxRows];
+};
+constexpr MxTab make_mx_tab() {
+    MxTab t{};
+    for (int i = 0; i < kPowHi; ++i) {
+        const uint64_t v = ipow(K, 64u * (unsigned)i);
+        t.w[kMxPowRow + 2 * i] = (uint32_t)v;
+        t.w[kMxPowRow + 2 * i + 1] = (uint32_t)(v >> 32);
+    }
+    for (int z = 0; z < 16; ++z) {
+        const uint64_t v = ipow(kKinv, (unsigned)z);
+        t.w[kMxInvRow + 2 * z] = (uint32_t)v;
+        t.w[kMxInvRow + 2 * z + 1] = (uint32_t)(v >> 32);
+    }
+    for (int m = 0; m < 4; ++m)
+        for (int half = 0; half < 2; ++half)
+            for (int r = 0; r < 4; ++r)   // class 4 (off the diagonal) stays zero
+                for (int j = 0; j < 16; ++j) {
+                    const int d = mx_digit(ipow(K, (unsigned)(63 - 16 * m - j)), 4 * half + r);
+                    t.w[kMxWRow + ((2 * m + half) * 5 + r) * 4 + (j >> 2)] |= (uint32_t)(d & 0xFF) << (8 * (j & 3));
+                }
+    return t;
+}
+__device__ const MxTab kMxTab = make_mx_tab();
+
+// V = sum_l S_l 2^(8 l) mod 2^64 from the limb sums (a: l = 0..3, b: l = 4..7): pairs in 32 bits
+// (|S_l + 256 S_(l+1)| < 2^29), then two 64-bit steps; of the upper half only the low word matters
+__device__ __forceinline__ uint64_t mx_combine(v4i32 a, v4i32 b) {
+    const int32_t p01 = a[0] + (int32_t)((uint32_t)a[1] << 8), p23 = a[2] + (int32_t)((uint32_t)a[3] << 8);
+    const uint32_t p45 = (uint32_t)b[0] + ((uint32_t)b[1] << 8), p67 = (uint32_t)b[2] + ((uint32_t)b[3] << 8);
+    const uint64_t lo = (uint64_t)((int64_t)p01 + (int64_t)((uint64_t)(int64_t)p23 << 16));
+    return lo + ((uint64_t)(p45 + (p67 << 16)) << 32);
+}
+
+// byte mask of a dword from a 4-bit byte-valid nibble
+__device__ __forceinline__ uint32_t mx_bytemask(uint32_t nib) { return ((nib * 0x00204081u) & 0x01010101u) * 0xFFu; }
+
+// The name [s_img, c_img) (image bytes) over 64-byte windows that end at E = c_img rounded up to 16 and
+// walk back from there: window k is the image bytes [E - 64 (k + 1), E - 64 k), four 16-byte pieces
+// that never cross an image row. Returns the sum over this lane's windows (lane gi of the line's Gl
+// takes windows gi, gi + Gl, ...) of V_k K^(64 k): the name's sdbm times K^z, z = E - c_img < 16
+// (the caller sums the G lanes of the line and multiplies by K^-z, mx_kinv).
+// Called by the whole wave in uniform control flow: the MFMAs are wave instructions, so the window
+// loop runs to the wave's longest trip count and lanes without a name (or past theirs) feed zeros.
+// Bytes before the name's first and from its end on are zeroed: a 64-bit map of the window's name
+// bytes per lane; a piece is skipped when no lane of the wave has a name byte in it, and masked only
+// when some lane's piece is not all name.
+// slot != nullptr: that granule is read into st after the first window's second piece (the tile's
+// record base, requested about a round trip before it is needed).
+template <class S>
+__device__ __forceinline__ uint64_t sdbm_mx(const S &sm, bool valid, int s_img, int c_img, int gi, int Gl,
+                                            const uint64_t *slot, uint64_t *st) {
+    const int lane = threadIdx.x & 63;
+    const int cls = (lane >> 4) == ((lane & 15) >> 2) ? (lane & 3) : 4;
+    const uint32_t *const wa = &sm.img[(kMxWRow + 4 * cls) * 17 + 16];
+    // the lane's state over its windows: f bytes of the window before the name (<= 0: none, >= 64: the
+    // window lies before the name, none left), the name ends at byte e of the window (> 48; >= 64:
+    // beyond it), the window's image row
+    const int E = (c_img + 15) & ~15;
+    const int w0 = E - 64 * (gi + 1);
+    int f = valid ? s_img - w0 : 64;
+    int e = c_img - w0;
+    const uint32_t *row = &sm.img[(w0 >> 6) * 17 + ((w0 >> 2) & 15)];
+    const int q3 = (E >> 4) & 3;   // the window's first piece within its image row
+    uint64_t h = 0;
+    bool first = true;
+    while (__ballot(f < 64) != 0ull) {
+        const bool on = f < 64;
+        const uint32_t *const rp = on ? row : &sm.img[0];
+        // bit i: byte i of the window is a name byte
+        const uint64_t bits = on ? (~0ull >> ((64 - min(e, 64)) & 63)) & (~0ull << (max(f, 0) & 63)) : 0ull;
+        v4i32 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const uint32_t p16 = (uint32_t)(bits >> (16 * m)) & 0xFFFFu;
+            if (m == 2 && first && slot) *st = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (__ballot(p16 != 0u) == 0ull) continue;   // no lane of the wave has a name byte in this piece
+            // piece m of the window: four dwords of one image row (the row's pad dword skipped)
+            const uint32_t *const pp = rp + 4 * m + ((q3 + m) >> 2);
+            v4i32 b = {(int)pp[0], (int)pp[1], (int)pp[2], (int)pp[3]};
+            if (__ballot(p16 != 0xFFFFu) != 0ull) {
+#pragma unroll
+                for (int d = 0; d < 4; ++d) b[d] &= (int)mx_bytemask((p16 >> (4 * d)) & 15u);
+            }
+            const uint32_t *const a0 = wa + (2 * m) * 20 * 17, *const a1 = wa + (2 * m + 1) * 20 * 17;
+            const v4i32 A0 = {(int)a0[0], (int)a0[17], (int)a0[34], (int)a0[51]};
+            acc0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(A0, b, acc0, 0, 0, 0);
+            const v4i32 A1 = {(int)a1[0], (int)a1[17], (int)a1[34], (int)a1[51]};
+            acc1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(A1, b, acc1, 0, 0, 0);
+        }
+        uint64_t v = mx_combine(acc0, acc1);
+        if (e > 64) {   // not the name's last window: times K^(64 k), k windows after this one
+            const int k = (e - 1) >> 6;
+            v *= ((uint64_t)sm.img[(kMxPowRow + 2 * k + 1) * 17 + 16] << 32) | sm.img[(kMxPowRow + 2 * k) * 17 + 16];
+        }
+        h += v;
+        f += 64 * Gl;
+        e += 64 * Gl;
+        row -= 17 * Gl;
+        first = false;
+    }
+    return h;
+}
+// K^-z (z < 16) from the pad tables
+template <class S>
+__device__ __forceinline__ uint64_t mx_kinv(const S &sm, int z) {
+    return ((uint64_t)sm.img[(kMxInvRow + 2 * z + 1) * 17 + 16] << 32) | sm.img[(kMxInvRow + 2 * z) * 17 + 16];
 }
 
 // 32-bit LDS address of a __shared__ object, and a two-dword LDS store at immediate dword offsets
@@ -1560,7 +1717,12 @@ __device__ __forceinline__ void tile_lines(const RouteParams &p, S &sm, const Ti
                 // (a staged 16-bit position reads 0xFFFF for "no colon": above every line end, as kNone is)
                 const bool fmt_ok = c != kNone && c < e;                                                // :140
                 uint64_t h = 0;
-                if (act && len_ok && fmt_ok && !(ABL & ABL_NO_HASH)) {
+                if constexpr (kMx<ABL>) {
+                    // the whole wave hashes (matrix instructions): lanes without a name feed zeros
+                    const bool mid = !(ABL & ABL_NO_MID_BASE) && !have_base;
+                    h = sdbm_mx(sm, act && len_ok && fmt_ok, s + kHalo, c + kHalo, gi, Gl, mid ? base_slot : nullptr,
+                                &st_early);
+                } else if (act && len_ok && fmt_ok && !(ABL & ABL_NO_HASH)) {
                     // sdbm of [s, c) = sum over 64-byte segments k of Horner(seg_k) * K^(c - end_k)
                     const int n = c - s, nseg = (n + 63) >> 6;
                     for (int k = gi; k < nseg; k += Gl) {
@@ -1575,7 +1737,11 @@ __device__ __forceinline__ void tile_lines(const RouteParams &p, S &sm, const Ti
                     const uint64_t v = shfl_xor64(h, d);
                     if (d < Gl) h += v;
                 }
-                if (act && gi == 0) finish(j, s, len, len_ok, fmt_ok, h);
+                if (act && gi == 0) {
+                    if constexpr (kMx<ABL>)   // the last window's z bytes past the name: K^-z
+                        if (len_ok && fmt_ok) h *= mx_kinv(sm, -(c + kHalo) & 15);
+                    finish(j, s, len, len_ok, fmt_ok, h);
+                }
             };
             auto line = [&](int jj, bool act, int gi, int Gl, int Gw) {
                 const int j = wbase + jj;
@@ -1794,14 +1960,19 @@ __attribute__((amdgpu_waves_per_eu((KernelTraits<ABL>::kMinWavesPerSimd), (Kerne
     const uint32_t t = (hdr.z ? (g >> 3) : g) - p.b[bi].tile0;   // the tile's index in its batch
     TileIn in;
     tile_issue<ABL>(p, bi, t, in, tid);
-    const uint32_t kp = tid < S::kPowWords ? ((const uint32_t *)p.kpow)[tid] : 0u;
+    const uint32_t kp = kMx<ABL> ? (tid < kMxRows ? kMxTab.w[tid] : 0u)
+                                 : (tid < S::kPowWords ? ((const uint32_t *)p.kpow)[tid] : 0u);
     // the scanner granule's load before the epoch's: the epoch's value is wanted at once (a wait for
     // every load issued before it, vmcnt counts in order), and a granule load issued after that wait
     // is a whole round trip more before the tile can publish its count (+5 % per C2 launch measured)
     in.sx = __hip_atomic_load(&p.ctl->scan_xcc[bi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t ep0 = __hip_atomic_load(&p.ctl->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (kEarlyArrive<ABL> && tid == 0) arrive_count_after(p, blockIdx.x, ep0);
-    if (tid < S::kPowWords) sm.put_pow(tid, kp);
+    if constexpr (kMx<ABL>) {
+        if (tid < kMxRows) sm.img[tid * 17 + 16] = kp;   // the matrix-core tables (sdbm_mx)
+    } else {
+        if (tid < S::kPowWords) sm.put_pow(tid, kp);
+    }
     if (!(ABL & (KV_ALIVE | KV_DEFER1 | KV_DEAD1)) && p.dead && p.dead < p.nds && tid < 4 * (int)kMagicLds) {   // the probe's first reciprocals (probe_shard)
         const uint32_t e = (uint32_t)tid >> 2;   // divisor nds - e >= 1: entries e < nds only
         if (e < p.nds) sm.img[(uint32_t)tid * 17 + 16] = ((const uint32_t *)&p.magic[p.nds - e])[tid & 3];
@@ -1816,17 +1987,26 @@ __attribute__((amdgpu_waves_per_eu((KernelTraits<ABL>::kMinWavesPerSimd), (Kerne
     uint64_t nlm, clm;
     uint32_t c_in;
     tile_load<ABL>(p, sm, in, ep0, g, nlm, clm, c_in);
-    tile_lines<ABL>(p, sm, in, ep0, g, nlm, clm, c_in);
-    mark_tile_end<ABL>(p, sm.img, p.b[bi], t, tid);   // MARK_LDS: the dead shards this tile's probes visited
+    // kMx: past the tile's count publish the epoch goes on in a scalar register, and the epilogue
+    // computes the tile index again (neither holds a VGPR through the line phase)
+    uint32_t ep1 = ep0, te = t;
+    if constexpr (kMx<ABL>) ep1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)ep0);
+    tile_lines<ABL>(p, sm, in, ep1, g, nlm, clm, c_in);
+    if constexpr (kMx<ABL>) {
+        uint32_t g2 = g;
+        asm volatile("" : "+s"(g2));
+        te = (hdr.z ? (g2 >> 3) : g2) - p.b[bi].tile0;
+    }
+    mark_tile_end<ABL>(p, sm.img, p.b[bi], te, tid);   // MARK_LDS: the dead shards this tile's probes visited
     if (kCountsHist<ABL> && p.hist) {   // the tile's key histogram for the packing (sr_route_pack_many)
         wg_barrier();
         const BatchDesc &bd = p.b[bi];
         if ((uint32_t)tid <= p.nds)
-            p.hist[(size_t)(p.nds + 1) * bd.sbase + (size_t)tid * bd.ntiles + t] = sm.hist[tid];
+            p.hist[(size_t)(p.nds + 1) * bd.sbase + (size_t)tid * bd.ntiles + te] = sm.hist[tid];
     }
     if (tid == 0) {
-        if (kEarlyArrive<ABL>) arrive_last(p, blockIdx.x, ep0);
-        else arrive(p, blockIdx.x, ep0);
+        if (kEarlyArrive<ABL>) arrive_last(p, blockIdx.x, ep1);
+        else arrive(p, blockIdx.x, ep1);
     }
     stamp<ABL>(p, tid, g, 9);
 }

@@ -158,6 +158,9 @@ int main(int argc, char **argv) {
             put("alive_no_lines_no_prologue", time_variant<KV_ALIVE | ABL_NO_LINES | ABL_NO_PROLOGUE>(c, 1, reps, 32));
             put("alive_load_only", time_variant<KV_ALIVE | ABL_LOAD_ONLY | ABL_NO_LOOKBACK | ABL_NO_PROLOGUE>(c, 1, reps, 32));
             put("alive_fake_base", time_variant<KV_ALIVE | ABL_FAKE_BASE>(c, 1, reps, 32));
+            // the sdbm's clean cost is alive_fake_base minus this row: without ABL_FAKE_BASE, ABL_NO_HASH also
+            // drops the mid-hash request of the record base and pays a wait_base round trip per tile
+            put("alive_fake_base_no_hash", time_variant<KV_ALIVE | ABL_FAKE_BASE | ABL_NO_HASH>(c, 1, reps, 32));
             put("read_kernel_s1", time_variant<0xFFFFu>(c, 1, reps));
             continue;
         }

@@ -3,10 +3,14 @@
 // (inline asm, so the instruction is exactly the one named). The grid fills every SIMD with
 // WAVES_PER_SIMD waves; the in-kernel clock comes from s_memtime / s_memrealtime (100 MHz).
 // Output: one JSON line, per op the SIMD cycles per wave-instruction (throughput, all waves).
+// `tools/ubench_ops coissue`: the MFMA / VALU co-issue case only (below).
 // Build: hipcc --offload-arch=gfx950 -O3 -o tools/ubench_ops tools/ubench_ops.hip
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+
+#include <string>
+#include <utility>
 
 constexpr int ITER = 2048;
 constexpr int kBlock = 256;
@@ -127,6 +131,85 @@ __global__ __launch_bounds__(kBlock) void kern(uint32_t seed, uint64_t *out, uin
     }
 }
 
+// Co-issue: what a wave of back-to-back v_mfma_i32_16x16x64_i8 costs the VALU waves of its SIMD.
+// One 1024-thread workgroup per CU (16 waves, four per SIMD): waves 0..11 issue ITER rounds of 8
+// independent v_mul_lo_u32 and time themselves (s_memtime); waves 12..15 (one per SIMD when waves are
+// dealt round-robin) are, by MODE, 0: idle (they exit), 1: back-to-back MFMAs for longer than the
+// VALU waves run, 2: the same VALU loop (what a fourth VALU wave costs, for comparison).
+// `tools/ubench_ops coissue` prints the VALU waves' cycles per instruction in each mode and the VALU
+// issue cycles one MFMA takes from the three waves beside it.
+template <int MODE>
+__global__ __launch_bounds__(1024) void coissue(uint32_t seed, uint64_t *out, uint64_t *clk) {
+    const int wave = threadIdx.x >> 6;
+    uint32_t a0 = threadIdx.x ^ seed, a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3, a4 = a0 + 4, a5 = a0 + 5, a6 = a0 + 6,
+             a7 = a0 + 7;
+    uint32_t b0 = seed * 3 + threadIdx.x, c0 = seed ^ 0x5A5A5A5Au;
+    typedef int v4i __attribute__((ext_vector_type(4)));
+    v4i acc0 = {(int)a0, 0, 0, 0}, acc1 = acc0, acc2 = acc0, acc3 = acc0;
+    v4i xa = {(int)b0, (int)c0, 1, 2}, xb = {(int)c0, 3, (int)b0, 4};
+    uint64_t dt = 0, nm = 0;
+    if (wave < 12 || MODE == 2) {
+        const uint64_t m0 = __builtin_amdgcn_s_memtime();
+        for (int it = 0; it < ITER; ++it) { BODY8("v_mul_lo_u32 %0, %1, %0") }
+        dt = __builtin_amdgcn_s_memtime() - m0;
+    } else if (MODE == 1) {
+        const uint64_t m0 = __builtin_amdgcn_s_memtime();
+        for (int it = 0; it < 2 * ITER; ++it) {
+            asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(acc0) : "v"(xa), "v"(xb));
+            asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(acc1) : "v"(xa), "v"(xb));
+            asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(acc2) : "v"(xa), "v"(xb));
+            asm volatile("v_mfma_i32_16x16x64_i8 %0, %1, %2, %0" : "+v"(acc3) : "v"(xa), "v"(xb));
+        }
+        dt = __builtin_amdgcn_s_memtime() - m0;
+        nm = 8ull * ITER;
+    }
+    out[blockIdx.x * 1024 + threadIdx.x] = (uint64_t)(a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7) ^
+                                           (uint64_t)(acc0[0] ^ acc1[1] ^ acc2[2] ^ acc3[3]);
+    if ((threadIdx.x & 63) == 0) {
+        clk[(blockIdx.x * 16 + wave) * 2] = dt;
+        clk[(blockIdx.x * 16 + wave) * 2 + 1] = nm;
+    }
+}
+
+template <int MODE>
+static void run_coissue(uint64_t *out, uint64_t *clk, uint64_t *hclk, double *valu_cyc, double *mfma_cyc) {
+    const int blocks = 256;
+    hipLaunchKernelGGL(coissue<MODE>, dim3(blocks), dim3(1024), 0, 0, 1u, out, clk);
+    hipLaunchKernelGGL(coissue<MODE>, dim3(blocks), dim3(1024), 0, 0, 2u, out, clk);
+    hipDeviceSynchronize();
+    hipMemcpy(hclk, clk, (size_t)blocks * 16 * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    double v = 0, m = 0;
+    for (int b = 0; b < blocks; ++b)
+        for (int w = 0; w < 16; ++w) {
+            const double dt = (double)hclk[(b * 16 + w) * 2];
+            if (w < 12) v += dt / (ITER * 8.0);
+            else if (MODE == 1) m += dt / (double)hclk[(b * 16 + w) * 2 + 1];
+        }
+    *valu_cyc = v / (blocks * 12.0);   // s_memtime ticks per VALU instruction of one wave (wall, not issue)
+    *mfma_cyc = m / (blocks * 4.0);    // ... per MFMA of the MFMA wave
+}
+
+static int main_coissue() {
+    uint64_t *out, *clk;
+    hipMalloc(&out, (size_t)256 * 1024 * 8);
+    hipMalloc(&clk, (size_t)256 * 16 * 16);
+    static uint64_t hclk[256 * 16 * 2];
+    double v0, v1, v2, m0, m1, m2;
+    run_coissue<0>(out, clk, hclk, &v0, &m0);
+    run_coissue<1>(out, clk, hclk, &v1, &m1);
+    run_coissue<2>(out, clk, hclk, &v2, &m2);
+    // three VALU waves share a SIMD: the SIMD issues one of their instructions every v / 3 ticks. Over one
+    // MFMA of the neighbour (m1 ticks) they issue m1 / (v1 / 3) instructions where they would have issued
+    // m1 / (v0 / 3) alone; the difference, in VALU issue slots of v0 / 3 ticks, is the MFMA's cost.
+    const double lost_insts = m1 / (v0 / 3.0) - m1 / (v1 / 3.0);
+    printf("{\"unit\": \"s_memtime ticks per wave instruction (wall time of the issuing wave)\", "
+           "\"valu_3_waves_alone\": %.3f, \"valu_3_waves_beside_mfma_wave\": %.3f, \"valu_4_waves\": %.3f, "
+           "\"mfma_wave_ticks_per_mfma\": %.3f, \"valu_instructions_lost_per_mfma\": %.3f, "
+           "\"simd_ticks_per_valu_issue_alone\": %.3f, \"valu_issue_ticks_lost_per_mfma\": %.3f}\n",
+           v0, v1, v2, m1, lost_insts, v0 / 3.0, lost_insts * v0 / 3.0);
+    return 0;
+}
+
 static const char *kNames[] = {
     "v_add_u32", "v_xor_b32", "v_mul_lo_u32", "v_mul_hi_u32", "v_mad_u64_u32", "v_mul_u32_u24", "v_mad_u32_u24",
     "v_dot4_i32_i8", "v_dot4_u32_u8", "v_perm_b32", "v_alignbyte_b32", "v_lshlrev_b64", "v_lshl_add_u64",
@@ -169,7 +252,8 @@ void run_all(int blocks, uint64_t *out, uint64_t *clk, uint64_t *hclk, std::inte
     ((run<OPS>(blocks, out, clk, hclk, first), first = 0), ...);
 }
 
-int main() {
+int main(int argc, char **argv) {
+    if (argc > 1 && std::string(argv[1]) == "coissue") return main_coissue();
     const int blocks = 256 * 8;   // 8 waves per SIMD (4 waves per block, 256 CUs)
     uint64_t *out, *clk;
     hipMalloc(&out, (size_t)blocks * kBlock * 8);
