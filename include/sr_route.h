@@ -125,6 +125,16 @@ int sr_set_layout(sr_ctx *ctx, int layout);
  * 0 before the first launch), or -EINVAL. */
 int sr_last_layout(const sr_ctx *ctx);
 
+/* Where the route kernel of the context's last route launch computed the sdbm name hash. Timing only:
+ * the hashes are identical bit for bit.
+ *   SR_HASH_VALU    the vector ALU (Horner steps);
+ *   SR_HASH_MATRIX  the matrix cores (i8 MFMA limb sums): the uniform and chunk layouts with every
+ *                   shard alive, or with two or more shards dead and their probes deferred.
+ * 0 before the first launch, or -EINVAL. */
+#define SR_HASH_VALU 1
+#define SR_HASH_MATRIX 2
+int sr_last_hash_engine(const sr_ctx *ctx);
+
 /* Host-memory batch: copy `bytes` (concatenated framed datagrams; the last byte must be '\n'
  * unless nbytes == 0) to the device, classify every line, copy min(n, max_records) records (and,
  * if hashes != NULL, the 64-bit sdbm name hashes; 0 for invalid lines) back, and synchronise.

@@ -47,7 +47,7 @@ assert RECORD_DTYPE.itemsize == 8
 # every function the header declares (tests check the library exports exactly these)
 ABI_FUNCTIONS = (
     "sr_frame_datagram", "sr_frame_datagrams", "sr_open", "sr_set_alive", "sr_set_stream", "sr_set_layout",
-    "sr_last_layout",
+    "sr_last_layout", "sr_last_hash_engine",
     "sr_route_batch", "sr_last_probed_dead", "sr_route_device", "sr_route_device_many", "sr_pack_by_owner",
     "sr_pack_many_by_owner", "sr_pack_packets", "sr_pack_packets_many", "sr_route_pack_batch", "sr_alloc_host", "sr_free_host", "sr_sync", "sr_close", "sr_version",
     "sr_pack_owner_sizes", "sr_pack_owner_scatter", "sr_regroup_launch",
@@ -63,6 +63,7 @@ SR_MAX_SLOTS = 65536
 SR_MAX_SLOT_STRIDE = 1 << 27
 SR_MAX_PACK_DOWNSTREAMS = 4096
 SR_LAYOUT_AUTO, SR_LAYOUT_UNIFORM, SR_LAYOUT_SEGMENTS, SR_LAYOUT_CHUNKS = 0, 1, 2, 3
+SR_HASH_VALU, SR_HASH_MATRIX = 1, 2   # sr_last_hash_engine
 SR_COMM_ID_BYTES = 128
 # sr_set_knob (developer / test knobs of one context; none changes a result)
 SR_KNOB_LB_SPIN, SR_KNOB_DEFER_PICKS, SR_KNOB_MTU_CHUNK, SR_KNOB_MTU_XCD, SR_KNOB_MTU_WALK = 1, 2, 3, 4, 5
@@ -217,6 +218,7 @@ def _load_route_lib() -> ctypes.CDLL:
         "sr_set_stream": (ctypes.c_int, [vp, vp]),
         "sr_set_layout": (ctypes.c_int, [vp, ctypes.c_int]),
         "sr_last_layout": (ctypes.c_int, [vp]),
+        "sr_last_hash_engine": (ctypes.c_int, [vp]),
         "sr_route_batch": (ctypes.c_int, [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, c_size_p, vp]),
         "sr_last_probed_dead": (ctypes.c_int, [vp, u64p]),
         "sr_route_device": (ctypes.c_int, [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp, vp]),
@@ -521,6 +523,11 @@ class Router:
         """sr_last_layout: the lane layout of the context's last route launch (1 uniform, 2 segments,
         3 chunks)."""
         return _check(self._lib.sr_last_layout(self._h), "sr_last_layout")
+
+    def last_hash_engine(self) -> int:
+        """sr_last_hash_engine: where the last route launch hashed names (SR_HASH_VALU = 1: vector ALU,
+        SR_HASH_MATRIX = 2: matrix cores; 0 before the first launch)."""
+        return _check(self._lib.sr_last_hash_engine(self._h), "sr_last_hash_engine")
 
     def route(self, data: bytes | np.ndarray, max_records: int | None = None, want_hashes: bool = False):
         """sr_route_batch on host memory. Returns (records[n] structured array, hashes or None, n)."""

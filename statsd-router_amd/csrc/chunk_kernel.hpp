@@ -11,7 +11,8 @@
 //
 // The sdbm hash of a name [s, c) is a polynomial in K = 65599 over its bytes (mod 2^64), so it
 // splits at the 64-byte chunk boundaries of a 16 KiB tile:
-//   * U(l): Horner of chunk l's 64 bytes, straight from the load registers (8 steps of 8 bytes);
+//   * U(l): Horner of chunk l's 64 bytes from its LDS row: 8 VALU steps of 8 bytes, or, in the
+//     every-shard-alive and KV_DEFER1 variants (kChunkMx), eight i8 MFMAs (sdbm_mx_row, route_kernel.hpp);
 //   * Suf_l(q): Horner of bytes [q, 64) of chunk l (the shorter side of q is read from the chunk's
 //     own LDS row: <= 32 bytes; the other side follows from U);
 //   * Y(l): Horner of every tile byte up to the end of chunk l, from one 64-bit block scan of
@@ -190,6 +191,9 @@ __global__ __launch_bounds__(256, 7) __attribute__((amdgpu_waves_per_eu(7, 8))) 
     // tile's loads: in a tile that some line crosses a chunk boundary of (most C5 tiles), asked for
     // only after the first barrier they were a dependent round trip of their own
     const uint64_t R = p.cpow[kCinv + tid], RI = p.cpow[kCinv + 256 + tid];
+    // kChunkMx: the A fragments of sdbm_mx_row for the pad dwords of rows kMxWRow .. kMxRows - 1
+    uint32_t mw = 0;
+    if constexpr (kChunkMx<ABL>) mw = kMxTab.w[tid < kMxRows ? tid : kMxRows - 1];
     // the dword before the tile (its last byte: does the tile start a line?), after the tables and at a
     // clamped address: loaded under `t > 0` it was a branch whose value the compiler waited for at once,
     // i.e. for every tile load, before the tables' loads were even issued (a round trip more per tile)
@@ -242,6 +246,9 @@ __global__ __launch_bounds__(256, 7) __attribute__((amdgpu_waves_per_eu(7, 8))) 
     }
     if (tid < kKpWords) ((uint32_t *)&sm.kp_lo[0])[tid] = kw;   // kp_lo | kp_hi are contiguous
     if (tid < 2 * kCinv) ((uint32_t *)&sm.kinv[0])[tid] = iw;
+    if constexpr (kChunkMx<ABL>) {   // read after B1 (these variants use no other pad dword)
+        if (tid >= kMxWRow && tid < kMxRows) sm.img[tid * 17 + 16] = mw;
+    }
     if (tid == 0) sm.head_nl = t == 0 || (pw >> 24) == 0x0Au ? 1u : 0u;
 
     // ---- line state: three u32 wave scans, the wave totals in LDS ------------------------------
@@ -295,12 +302,19 @@ __global__ __launch_bounds__(256, 7) __attribute__((amdgpu_waves_per_eu(7, 8))) 
     const bool before = prevnl == 0 && !sm.head_nl;                      // ... which began in an earlier tile
     const uint32_t ih = before ? kSlotBefore : (uint32_t)prevnl >> 6;   // its slot
 
-    // ---- U: Horner of the chunk's 64 bytes, from its LDS row. After the count is published: a
+    // ---- U: Horner of the chunk's 64 bytes, from its LDS row (kChunkMx: on the matrix cores, with the A
+    // fragments staged in the pad dwords at tile entry). After the count is published: a
     // tile's record base follows its predecessors' counts through the scanner, so the earlier the
     // counts go out, the less the tiles wait for their bases when they write their records ----------
     const uint32_t *const row = &sm.img[tid * 17];
     uint64_t U;
-    {
+    if constexpr (kChunkMx<ABL>) {
+        // on the matrix cores: all four waves, in uniform control flow; a chunk past the batch's end
+        // feeds the zeros its row holds (U = 0)
+        U = sdbm_mx_row(sm.img, row);
+        if (ABL & CH_ABL_NO_U) U = row[0];
+        pin64(U);
+    } else {
         uint32_t x[16];
 #pragma unroll
         for (int i = 0; i < 16; ++i) x[i] = row[i];

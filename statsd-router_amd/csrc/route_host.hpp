@@ -89,6 +89,7 @@ struct DeviceState {
     int layout_mode = 0;
     bool seg_on = false;             // AUTO: mixed-length traffic seen, KV_SEGMENTS launched
     int last_layout = 0;             // the variant of the last launch (SR_LAYOUT_UNIFORM / _SEGMENTS)
+    int last_hash_engine = 0;        // its name hash: SR_HASH_VALU / SR_HASH_MATRIX (0: no launch yet)
     uint32_t seen_seq = 0;
     uint64_t launches = 0;
     uint32_t *h_layout = nullptr;    // pinned, device-mapped: {sequence, tiles weighed, tiles segmented}
@@ -362,6 +363,19 @@ struct DeviceState {
     bool replay_wants_hashes() const { return dead && dead < nds && !marks_in_kernel(); }
 };
 
+// One route kernel launch of variant M, and what sr_last_hash_engine then reports: kHashEngine<M>, the
+// predicate the kernel itself branches on.
+template <unsigned M>
+inline void launch_route_variant(DeviceState &ds, const RouteParams &p, hipStream_t stream) {
+    hipLaunchKernelGGL((route_kernel<kBlock, M>), dim3(p.total_blocks), dim3(kBlock), 0, stream, p);
+    ds.last_hash_engine = kHashEngine<M>;
+}
+template <unsigned M>
+inline void launch_chunk_variant(DeviceState &ds, const RouteParams &p, hipStream_t stream) {
+    hipLaunchKernelGGL((route_chunk_kernel<M>), dim3(p.total_blocks), dim3(256), 0, stream, p);
+    ds.last_hash_engine = kHashEngine<M>;
+}
+
 // Launch the route kernel over the batches of p (tile ranges assigned here; empty batches get a
 // zero line count without a kernel). With more than kOverlay dead shards every batch is launched
 // on its own so that the deferred-probe list holds one batch at a time.
@@ -505,27 +519,27 @@ inline int launch_route(DeviceState &ds, const RouteParams &in, hipStream_t stre
         // its probe stops after the first picks: with two or more dead shards it needs the deferral
         // (no scratch for it, e.g. inside a stream capture: the uniform kernel probes in full)
         if (ds.dead >= 2 && ds.dead < ds.nds && !p.defer)
-            hipLaunchKernelGGL((route_kernel<kBlock, KV_UNIFORM>), dim3(p.total_blocks), dim3(kBlock), 0, stream, p);
+            launch_route_variant<KV_UNIFORM>(ds, p, stream);
         else if (defer1)
-            hipLaunchKernelGGL((route_chunk_kernel<kD1>), dim3(p.total_blocks), dim3(256), 0, stream, p);
+            launch_chunk_variant<kD1>(ds, p, stream);
         else if (dead1)
-            hipLaunchKernelGGL((route_chunk_kernel<kK1>), dim3(p.total_blocks), dim3(256), 0, stream, p);
+            launch_chunk_variant<kK1>(ds, p, stream);
         else
-            hipLaunchKernelGGL((route_chunk_kernel<ABL>), dim3(p.total_blocks), dim3(256), 0, stream, p);
+            launch_chunk_variant<ABL>(ds, p, stream);
     } else if constexpr ((ABL & KV_PICKS) != 0) {
         // the picks-only variant needs the deferral once two or more shards are dead
         if (ds.dead >= 2 && ds.dead < ds.nds && !p.defer)
-            hipLaunchKernelGGL((route_kernel<kBlock, (ABL & ~KV_PICKS)>), dim3(p.total_blocks), dim3(kBlock), 0, stream, p);
+            launch_route_variant<(ABL & ~KV_PICKS)>(ds, p, stream);
         else if (defer1)
-            hipLaunchKernelGGL((route_kernel<kBlock, kD1>), dim3(p.total_blocks), dim3(kBlock), 0, stream, p);
+            launch_route_variant<kD1>(ds, p, stream);
         else if (dead1 && p.hist)
-            hipLaunchKernelGGL((route_kernel<kBlock, kK1 | KV_HIST1>), dim3(p.total_blocks), dim3(kBlock), 0, stream, p);
+            launch_route_variant<kK1 | KV_HIST1>(ds, p, stream);
         else if (dead1)
-            hipLaunchKernelGGL((route_kernel<kBlock, kK1>), dim3(p.total_blocks), dim3(kBlock), 0, stream, p);
+            launch_route_variant<kK1>(ds, p, stream);
         else
-            hipLaunchKernelGGL((route_kernel<kBlock, ABL>), dim3(p.total_blocks), dim3(kBlock), 0, stream, p);
+            launch_route_variant<ABL>(ds, p, stream);
     } else {
-        hipLaunchKernelGGL((route_kernel<kBlock, ABL>), dim3(p.total_blocks), dim3(kBlock), 0, stream, p);
+        launch_route_variant<ABL>(ds, p, stream);
     }
     if (hipGetLastError() != hipSuccess) return -EIO;
     // the key histograms exist only where route_kernel counted them: every shard alive, or exactly one

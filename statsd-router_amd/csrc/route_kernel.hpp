@@ -49,10 +49,11 @@
 //   * Every workgroup arrives on 8-way sharded counters without waiting; the last block waits for
 //     all arrivals and advances the context's epoch, so stale granules of earlier launches are never
 //     mistaken for current ones, with or without graph replay.
-// Matrix cores: the every-shard-alive uniform variant (C2, C3, C4) hashes names with
-// v_mfma_i32_16x16x64_i8 (sdbm_mx: sdbm as signed-digit limb sums, two MFMAs per 16 name bytes), which
-// takes the multiply-adds out of the VALU stream the launch is bound by; every other variant keeps the
-// VALU Horner (sdbm_img). The rest is byte work on VALU + LDS.
+// Matrix cores: the every-shard-alive uniform variant (C2, C3, C4) and the uniform KV_DEFER1 variant (kMx)
+// hash names with v_mfma_i32_16x16x64_i8 (sdbm_mx: sdbm as signed-digit limb sums, two MFMAs per 16 name
+// bytes), which takes the multiply-adds out of the VALU stream the launch is bound by; route_chunk_kernel's
+// every-shard-alive and KV_DEFER1 variants (kChunkMx) do the same for U(l), each lane's 64 bytes
+// (sdbm_mx_row). Every other variant keeps the VALU Horner (sdbm_img). The rest is byte work on VALU + LDS.
 //
 // Variants. The kernels' template argument is a mask of the KV_* bits below (ABL_* bits join them in
 // developer builds only). All variants write identical records; the library holds 12 instantiations of
@@ -74,7 +75,8 @@
 
 #include "../../include/sr_route.h"
 
-// 1: route_kernel<256, KV_UNIFORM | KV_ALIVE> hashes names on the matrix cores (sdbm_mx); 0: VALU Horner
+// 1: the variants of kMx and kChunkMx hash names on the matrix cores (sdbm_mx, sdbm_mx_row); 0: VALU Horner
+// everywhere
 #ifndef SR_SDBM_MFMA
 #define SR_SDBM_MFMA 1
 #endif
@@ -774,9 +776,22 @@ __device__ __forceinline__ void mark_tile_end(const RouteParams &p, const uint32
 // (ABL_STAMPS, the diagnostic build of tools/stamps_route.hip, keeps the shape of what it stamps.)
 template <unsigned ABL>
 constexpr bool kOcc8 = (ABL & ~ABL_STAMPS) == (KV_UNIFORM | KV_ALIVE);
-// kMx: that variant hashes names on the matrix cores (sdbm_mx below; -DSR_SDBM_MFMA=0 keeps the VALU Horner)
+// kMx: the route_kernel variants that hash names on the matrix cores (sdbm_mx below; -DSR_SDBM_MFMA=0
+// keeps the VALU Horner): that one, and the uniform KV_DEFER1 variant (two or more dead shards), whose
+// probe takes kernel arguments and leaves the pad dwords free for the tables just the same.
 template <unsigned ABL>
-constexpr bool kMx = SR_SDBM_MFMA != 0 && kOcc8<ABL>;
+constexpr bool kMx = SR_SDBM_MFMA != 0 &&
+                     (kOcc8<ABL> || (ABL & ~ABL_STAMPS) == (KV_UNIFORM | KV_PICKS | KV_DEFER1));
+// kChunkMx: the route_chunk_kernel variants whose U(l) runs on the matrix cores (sdbm_mx_row): every
+// shard alive, and KV_DEFER1. Their pad dwords are unused; the general variant's hold the probe's
+// reciprocals and alive words, KV_DEAD1's mark rows overlap the A fragments' rows.
+template <unsigned ABL>
+constexpr bool kChunkMx = SR_SDBM_MFMA != 0 && ((ABL & kKvBits) == (KV_CHUNKS | KV_ALIVE) ||
+                                                (ABL & kKvBits) == (KV_CHUNKS | KV_DEFER1));
+// what sr_last_hash_engine reports for a kernel's variant mask (SR_HASH_VALU / SR_HASH_MATRIX): the
+// predicates the kernels themselves branch on
+template <unsigned ABL>
+constexpr int kHashEngine = ((ABL & KV_CHUNKS) ? kChunkMx<ABL> : kMx<ABL>) ? SR_HASH_MATRIX : SR_HASH_VALU;
 
 template <bool SLIM = false>
 struct SmemT {
@@ -929,7 +944,9 @@ constexpr int kMxPowRow = 0;                 // K^(64 i): low word at row 2 i, h
 constexpr int kMxInvRow = 2 * kPowHi;        // K^-z, z < 16
 constexpr int kMxWRow = kMxInvRow + 32;      // A fragments: row kMxWRow + ((2 m + half) * 5 + class) * 4 + word
 constexpr int kMxRows = kMxWRow + 8 * 5 * 4;
-static_assert(kMxRows <= SmemT<true>::kRows && kMxRows <= kBlock, "the matrix-core tables in the pad dwords, one per thread");
+// (each kernel asserts kMxRows against its own image's row count)
+static_assert(kMxRows <= kBlock, "the matrix-core tables in the pad dwords, one per thread");
+static_assert(kMxWRow >= 0 && kMxRows <= 256, "the A fragments within route_chunk_kernel's 256 image rows");
 
 // digit l of v in balanced base 256 (digits in [-128, 127])
 constexpr int mx_digit(uint64_t v, int l) {
@@ -976,6 +993,33 @@ __device__ __forceinline__ uint64_t mx_combine(v4i32 a, v4i32 b) {
     return lo + ((uint64_t)(p45 + (p67 << 16)) << 32);
 }
 
+// A fragment (2 m + half) of the calling lane from the pad tables of image `img`: its four words sit in
+// four consecutive rows; a lane off the block diagonal reads the zero fragment (class 4)
+__device__ __forceinline__ v4i32 mx_frag(const uint32_t *img, int frag) {
+    const int lane = threadIdx.x & 63;
+    const int cls = (lane >> 4) == ((lane & 15) >> 2) ? (lane & 3) : 4;
+    const uint32_t *const a = &img[(kMxWRow + (frag * 5 + cls) * 4) * 17 + 16];
+    return v4i32{(int)a[0], (int)a[17], (int)a[34], (int)a[51]};
+}
+
+// U = sum_p b_p K^(63 - p) over the 64 bytes of one image row (signed bytes): the sdbm of the row from
+// h = 0. One window whose four pieces are the row's four 16-byte quarters, every byte a data byte: no
+// masks, no loop and no K^-z; eight MFMAs and one combine. Called by whole waves in uniform control
+// flow; a lane whose row holds zeros gets 0. (route_chunk_kernel's U(l), chunk_kernel.hpp)
+__device__ __forceinline__ uint64_t sdbm_mx_row(const uint32_t *img, const uint32_t *row) {
+    v4i32 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const v4i32 b = {(int)row[4 * m], (int)row[4 * m + 1], (int)row[4 * m + 2], (int)row[4 * m + 3]};
+        acc0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(mx_frag(img, 2 * m), b, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(mx_frag(img, 2 * m + 1), b, acc1, 0, 0, 0);
+        // one piece's operands in flight: hoisted to the top, the 48 LDS dwords of all four spill the
+        // chunk kernel out of its 72 VGPRs
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    return mx_combine(acc0, acc1);
+}
+
 // byte mask of a dword from a 4-bit byte-valid nibble
 __device__ __forceinline__ uint32_t mx_bytemask(uint32_t nib) { return ((nib * 0x00204081u) & 0x01010101u) * 0xFFu; }
 
@@ -994,9 +1038,6 @@ __device__ __forceinline__ uint32_t mx_bytemask(uint32_t nib) { return ((nib * 0
 template <class S>
 __device__ __forceinline__ uint64_t sdbm_mx(const S &sm, bool valid, int s_img, int c_img, int gi, int Gl,
                                             const uint64_t *slot, uint64_t *st) {
-    const int lane = threadIdx.x & 63;
-    const int cls = (lane >> 4) == ((lane & 15) >> 2) ? (lane & 3) : 4;
-    const uint32_t *const wa = &sm.img[(kMxWRow + 4 * cls) * 17 + 16];
     // the lane's state over its windows: f bytes of the window before the name (<= 0: none, >= 64: the
     // window lies before the name, none left), the name ends at byte e of the window (> 48; >= 64:
     // beyond it), the window's image row
@@ -1026,11 +1067,8 @@ __device__ __forceinline__ uint64_t sdbm_mx(const S &sm, bool valid, int s_img, 
 #pragma unroll
                 for (int d = 0; d < 4; ++d) b[d] &= (int)mx_bytemask((p16 >> (4 * d)) & 15u);
             }
-            const uint32_t *const a0 = wa + (2 * m) * 20 * 17, *const a1 = wa + (2 * m + 1) * 20 * 17;
-            const v4i32 A0 = {(int)a0[0], (int)a0[17], (int)a0[34], (int)a0[51]};
-            acc0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(A0, b, acc0, 0, 0, 0);
-            const v4i32 A1 = {(int)a1[0], (int)a1[17], (int)a1[34], (int)a1[51]};
-            acc1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(A1, b, acc1, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(mx_frag(sm.img, 2 * m), b, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(mx_frag(sm.img, 2 * m + 1), b, acc1, 0, 0, 0);
         }
         uint64_t v = mx_combine(acc0, acc1);
         if (e > 64) {   // not the name's last window: times K^(64 k), k windows after this one
@@ -1915,6 +1953,7 @@ __global__ __launch_bounds__(kBlock, (KernelTraits<ABL>::kMinWavesPerSimd))
 __attribute__((amdgpu_waves_per_eu((KernelTraits<ABL>::kMinWavesPerSimd), (KernelTraits<ABL>::kMaxWavesPerSimd)))) void route_kernel(RouteParams p) {
     static_assert(BLOCK == kBlock, "one workgroup size");
     using S = SmemT<kOcc8<ABL>>;
+    static_assert(!kMx<ABL> || kMxRows <= S::kRows, "the matrix-core tables in the pad dwords of this variant's image");
     __shared__ S sm;
     const int tid = threadIdx.x;
     const int lane = tid & 63;

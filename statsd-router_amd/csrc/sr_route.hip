@@ -279,6 +279,7 @@ int sr_set_layout(sr_ctx *c, int layout) {
 }
 
 int sr_last_layout(const sr_ctx *c) { return c ? c->ds.last_layout : -EINVAL; }
+int sr_last_hash_engine(const sr_ctx *c) { return c ? c->ds.last_hash_engine : -EINVAL; }
 
 int sr_set_knob(sr_ctx *c, int knob, int64_t v) {
     if (!c) return -EINVAL;
