@@ -39,6 +39,9 @@ static int log_prefix(char *buf, int level) {
     return l;
 }
 
+/* the prefix a message of `level` gets now (SR_DEVICE_LOG: asked once per batch); buf has SR_LOG_BUF_SIZE bytes */
+size_t sr_log_prefix(int level, char *buf) { return (size_t)log_prefix(buf, level); }
+
 void sr_log(int level, const char *fmt, ...) {
     if (level < sr_log_level) return;
     char buf[SR_LOG_BUF_SIZE];

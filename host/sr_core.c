@@ -62,6 +62,11 @@ struct sr_core {
     size_t slot_n[2];                        /* slots of the batch; 0: the buffer holds framed bytes */
     uint64_t *ping_hash;                     /* TRACE: the ping names' hashes                      */
     int payloads;                            /* sr_core_set_payloads: packets from the slot's arena */
+    int devlog;                              /* sr_core_set_device_log: batches' log text from the GPU */
+    sr_core_log_prefix_fn log_prefix;        /* block mode: the prefixes, asked at submission      */
+    sr_core_log_block_fn log_block;          /* block mode: a batch's whole text in one call       */
+    int log_host[2];                         /* the slot's batch could not be staged: the host formats it */
+    uint64_t log_device_n, log_host_n;       /* sr_core_device_log_stats                            */
     int host_fills;                          /* the host changed pending buffers since the last  */
                                              /* submission: upload them with the next one         */
     uint16_t *fill16;
@@ -308,6 +313,31 @@ static int trace_batch(sr_core *c, int slot, const uint8_t *framed, size_t nbyte
     return 0;
 }
 
+/* sr_core_set_device_log: the batch's messages as the GPU wrote them into the slot (sr_route_pack_logtext),
+ * to the block callback in one call or to the log callback one by one. Not 0: the text or its index did not
+ * fit, or the slot has none; the caller formats the batch on the host. */
+static int device_log(sr_core *c, int slot) {
+    const uint8_t *text;
+    const uint32_t *offs;
+    const uint8_t *lv;
+    uint64_t total = 0;
+    size_t n = 0;
+    int rc = c->log_host[slot] ? -ENOSPC : sr_route_pack_logtext(c->ctx, slot, &text, &total, &offs, &lv, &n);
+    if (rc) {
+        c->log_host_n++;
+        return rc;
+    }
+    c->log_device_n++;
+    if (c->log_block) {
+        if (n) c->log_block(c->user, (const char *)text, (size_t)total, n);
+    } else {
+        for (size_t i = 0; i < n; i++)
+            c->log(c->user, lv[i], (const char *)text + offs[i], (size_t)(offs[i + 1] - offs[i]) - 1);
+    }
+    c->dg_n[slot] = 0;
+    return 0;
+}
+
 /* The host's half of a batch (udp_read_cb's per-line side effects, sr-main.c:175-189, for a whole
  * batch): drop probed dead buffers, the log lines in input order, then the packets per downstream. */
 static void complete(sr_core *c, int slot, const uint8_t *framed, size_t nbytes, const sr_pack_result *r) {
@@ -315,7 +345,9 @@ static void complete(sr_core *c, int slot, const uint8_t *framed, size_t nbytes,
     drop_probed(c);
     /* without the TRACE inputs (the slot was not traced) the WARN lines still come, from the sorted
      * records' unrouted tail, in input order */
-    if ((!c->trace || trace_batch(c, slot, framed, nbytes) != 0) && c->log_level <= SR_WARN)
+    if (c->devlog && device_log(c, slot) == 0) {
+        /* logged */
+    } else if ((!c->trace || trace_batch(c, slot, framed, nbytes) != 0) && c->log_level <= SR_WARN)
         for (size_t i = r->n_valid; i < r->n_records; i++) warn_line(c, slot, framed, &r->sorted[i]);
     /* sr_core_set_payloads: the packets' lines laid end to end by the GPU, packet q at
      * arena[offs[q] + carry, offs[q + 1]) (the carry's room is unwritten: the host holds those bytes) */
@@ -376,6 +408,25 @@ static int submit(sr_core *c, int slot, const uint8_t *framed, size_t nbytes) {
     if (c->host_fills) {   /* nothing is in flight here: the host's fills are current */
         for (uint32_t s = 0; s < c->n; s++) c->fill16[s] = (uint16_t)c->ds[s].fill;
         fill = c->fill16;
+    }
+    if (c->devlog) {   /* staged for this submission only */
+        /* A batch that cannot be staged (more datagram ends than the slot's staging holds, or a staging
+         * error) is still routed: the host formats its log, as for a text that did not fit. */
+        int rc = 0;
+        c->log_host[slot] = 0;
+        if (c->log_block) {
+            char pfx[2 * SR_LOG_MAX_PREFIX];
+            size_t tl = c->trace ? c->log_prefix(c->user, SR_TRACE, pfx, SR_LOG_MAX_PREFIX) : 0;
+            if (tl > SR_LOG_MAX_PREFIX) tl = SR_LOG_MAX_PREFIX;
+            size_t wl = c->log_prefix(c->user, SR_WARN, pfx + tl, SR_LOG_MAX_PREFIX);
+            if (wl > SR_LOG_MAX_PREFIX) wl = SR_LOG_MAX_PREFIX;
+            rc = sr_route_pack_set_prefix(c->ctx, slot, (const uint8_t *)pfx, tl, (const uint8_t *)pfx + tl, wl);
+        }
+        if (!rc && c->trace && !c->slot_n[slot]) {
+            if (c->dg_n[slot] > SR_MAX_SLOTS) rc = -ENOSPC;
+            else rc = sr_route_pack_set_ends(c->ctx, slot, c->dg_ends[slot], c->dg_n[slot]);
+        }
+        if (rc) c->log_host[slot] = 1;
     }
     int rc = c->slot_n[slot] ? sr_route_pack_submit_slots(c->ctx, slot, c->in[slot], SR_DATA_BUF_SIZE, c->slot_lens[slot],
                                                           c->slot_n[slot], fill)
@@ -540,6 +591,32 @@ int sr_core_set_payloads(sr_core *c, int on) {
         sr_pack_result r;
         if ((rc = sr_route_pack_submit(c->ctx, k, NULL, 0, NULL)) || (rc = sr_route_pack_result(c->ctx, k, &r))) return rc;
     }
+    return 0;
+}
+
+int sr_core_set_device_log(sr_core *c, int on, size_t text_cap, sr_core_log_prefix_fn prefix, sr_core_log_block_fn block) {
+    if (!c || (on && block && !prefix)) return -EINVAL;
+    if (c->in_flight >= 0) return -EBUSY;
+    /* a core that logs nothing of a batch (log_level above WARN, or no callback at all) has nothing to format */
+    const int wanted = on && c->log_level <= SR_WARN && (block || c->log);
+    int rc = sr_set_logtext(c->ctx, wanted ? (c->log_level <= SR_TRACE ? SR_TRACE : SR_WARN) : -1, text_cap,
+                            wanted ? (block ? SR_CORE_LOG_MAX_MSG : (uint32_t)c->msg_cap - 1) : 0);   /* core_log's cut */
+    if (rc) return rc;
+    c->devlog = wanted ? 1 : 0;
+    c->log_prefix = wanted ? prefix : NULL;
+    c->log_block = wanted ? block : NULL;
+    /* both slots' arenas allocated now (an empty batch each; the device's pending bytes carry over) */
+    for (int k = 0; wanted && k < 2; k++) {
+        sr_pack_result r;
+        if ((rc = sr_route_pack_submit(c->ctx, k, NULL, 0, NULL)) || (rc = sr_route_pack_result(c->ctx, k, &r))) return rc;
+    }
+    return 0;
+}
+
+int sr_core_device_log_stats(const sr_core *c, uint64_t *device_batches, uint64_t *host_batches) {
+    if (!c) return -EINVAL;
+    if (device_batches) *device_batches = c->log_device_n;
+    if (host_batches) *host_batches = c->log_host_n;
     return 0;
 }
 

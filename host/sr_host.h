@@ -26,6 +26,7 @@
 extern int sr_log_level;
 void sr_log(int level, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 void sr_log_text(int level, const char *msg, size_t len);
+size_t sr_log_prefix(int level, char *buf);
 
 /* ---- downstream health (sr-health-client.c) ---- */
 typedef struct sr_health_client {
@@ -58,6 +59,8 @@ typedef struct sr_config {
                                                 /* batch before returning (no double buffering; A/B)    */
     int dt_device_framing;                      /* SR_DEVICE_FRAMING=1: datagrams stay in their recvmmsg slots and */
                                                 /* are framed on the GPU (sr_core_submit_slots); off by default    */
+    int dt_device_log;                          /* SR_DEVICE_LOG=1: a batch's log text is written on the GPU and goes */
+                                                /* to stdout in one write (sr_core_set_device_log); off by default   */
     int dt_yield;                               /* full batches per read event before timers run (0: no cap) */
     double dt_yield_s;                          /* seconds per read event before timers run (0: no cap)  */
     /* alive bits published by the health checker to the data threads */

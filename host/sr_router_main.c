@@ -111,6 +111,22 @@ static void on_log(void *user, int level, const char *msg, size_t len) {
     sr_log_text(level, msg, len);
 }
 
+/* SR_DEVICE_LOG=1: the prefix of the batch being submitted, and its whole text in one write */
+static size_t on_log_prefix(void *user, int level, char *dst, size_t cap) {
+    (void)user;
+    char buf[SR_LOG_BUF_SIZE];
+    size_t l = sr_log_prefix(level, buf);
+    if (l > cap) l = cap;
+    memcpy(dst, buf, l);
+    return l;
+}
+
+static void on_log_block(void *user, const char *text, size_t len, size_t n_msgs) {
+    (void)user, (void)n_msgs;
+    fwrite(text, 1, len, stdout);
+    fflush(stdout);
+}
+
 static void refresh_alive(data_thread *d) {
     const uint64_t g = atomic_load_explicit(&d->c->alive_gen, memory_order_acquire);
     if (g == d->alive_gen) return;
@@ -340,6 +356,10 @@ void *sr_data_thread(void *arg) {
         sr_log(SR_ERROR, "%s: sr_core_open() failed %s", fn, strerror(-rc));
         return thread_fail(d, 1);
     }
+    if (c->dt_device_log && (rc = sr_core_set_device_log(d->core, 1, 0, on_log_prefix, on_log_block))) {
+        sr_log(SR_ERROR, "%s: sr_core_set_device_log() failed %s", fn, strerror(-rc));
+        return thread_fail(d, 1);
+    }
     d->slot = 0;
     d->batch = sr_core_slot_buffer(d->core, 0, &d->cap);
     d->trace = sr_log_level <= SR_TRACE;
@@ -414,6 +434,8 @@ int main(int argc, char *argv[]) {
     config.dt_sync = ds && ds[0] == '1';
     const char *df = getenv("SR_DEVICE_FRAMING");
     config.dt_device_framing = df && df[0] == '1';
+    const char *dl = getenv("SR_DEVICE_LOG");
+    config.dt_device_log = dl && dl[0] == '1';
     config.dt_yield = dy ? atoi(dy) : 0;
     config.dt_yield_s = dys ? atof(dys) : READ_EVENT_SECONDS;
 

@@ -597,6 +597,98 @@ int sr_frame_slots(sr_ctx *ctx, const sr_slot_batch *b);
 int sr_route_pack_submit_slots(sr_ctx *ctx, int slot, const uint8_t *slots, size_t stride,
                                const uint16_t *lens, size_t count, const uint16_t *fill);
 
+/* ---- log text on the device ------------------------------------------------------------------------ */
+/* At log_level TRACE (the reference's default, sr-init.c:252) udp_read_cb writes more log text than it routes:
+ * "got packet" per datagram (sr-main.c:174) and two find_downstream messages per valid line (:91,102), next to
+ * the WARN messages of the lines it drops (:115,142,184). sr_format_log writes a routed batch's messages on
+ * the device, in the reference's order and bytes, back to back into one arena: datagrams in order, inside each
+ * its lines in order, and per line
+ *   TRACE "udp_read_cb: got packet " + the datagram's framed bytes, when the line starts a datagram: its offset
+ *         is the end before d_ends[g] and d_ends[g] is greater (an empty datagram gets none; lines at or after
+ *         the last end, or all lines with d_ends == NULL, get none);
+ *   then  route SR_ROUTE_INVALID_LENGTH: WARN "udp_read_cb: invalid length %d of metric " + the line, '\n' included;
+ *         route SR_ROUTE_INVALID_FORMAT: WARN "process_data_line: invalid metric " + the line without its '\n';
+ *         any other route: TRACE "find_downstream: hash = %lx, length = %d, line = " + the line, '\n' included,
+ *         followed by TRACE "find_downstream: pushing to downstream %d" when route < n_downstreams (the
+ *         context's), else WARN "find_downstream: all downstreams are dead".
+ * A run of input bytes is printed as "%.*s" prints it: it stops before its first NUL byte. With min_level =
+ * 3 (WARN) only the WARN messages are written, in the same order, and d_hashes may be NULL.
+ * On the wire a message is prefix[level] + text + '\n': d_prefix holds prefix_len[0] bytes for TRACE followed
+ * by prefix_len[1] bytes for WARN (each at most SR_LOG_MAX_PREFIX). max_msg > 0 cuts prefix + text to max_msg
+ * bytes before the '\n' (2047: log_msg's 2048-byte buffer, sr-util.c:14-27); it must exceed both prefix
+ * lengths.
+ *   d_text / text_cap : the messages. Nothing at or past min(*d_total, text_cap) is written;
+ *   d_total           : the bytes needed; the text is complete iff *d_total <= text_cap;
+ *   d_n_msgs          : the messages; the index is complete iff *d_n_msgs <= max_msgs;
+ *   d_offsets         : NULL, or max_msgs + 1 u32: entry i < min(n, max_msgs) is the first byte of message i,
+ *                       entry min(n, max_msgs) the end of the last indexed message (the total when the index
+ *                       is complete); later entries are not written. Entries are 32-bit: an index serves
+ *                       texts below 4 GiB (the totals are 64-bit);
+ *   d_levels          : NULL, or max_msgs u8: 0 (TRACE) or 3 (WARN) per indexed message.
+ * Only min(*d_n_records, max_records, nbytes) records are read (a line has at least one byte, so a real
+ * record count never exceeds nbytes; the third bound keeps the grid finite for a wrong one); every byte read
+ * lies inside [0, nbytes) whatever the records say. nbytes <= max_batch_bytes and <= 2^30. Inputs and outputs may sit at any byte alignment
+ * (d_recs, d_hashes, d_ends, d_offsets, d_total, d_n_msgs at their types').
+ * Asynchronous on the context's stream. The first call allocates the context's scan scratch, once and at its
+ * full size (not inside stream capture); later calls allocate nothing and can be captured in a graph.
+ * Returns 0, -EINVAL, -ENOMEM, -EIO.
+ *
+ * Room that always suffices for a framed batch and its own records:
+ *   SR_LOG_MAX_MSGS: a line yields one message, or two when it passes the length gate (>= 6 bytes), so at most
+ *     one per byte; plus one "got packet" per datagram.
+ *   SR_LOG_TEXT_CAPACITY: with P = the longer prefix, a line of L bytes costs at most L * (P + 42) bytes: a
+ *     one-byte line is P + "udp_read_cb: invalid length 1 of metric " (40) + the byte + '\n' = P + 42; 2..5
+ *     bytes: P + 40 + L + 1; an invalid length of 1450 or more: P + 44 + L + 1; an invalid metric (L >= 6):
+ *     P + 34 + L; a routed line (L >= 6): at most P + 64 + L + 1 with a 16-digit hash and a 4-digit length,
+ *     then at most P + 45 ("pushing to downstream 65532" + '\n'), together 2 P + 110 + L <= L (P + 42). A datagram costs
+ *     P + 24 + its bytes + 1. The lines' bytes and the datagrams' bytes are each at most nbytes. */
+#define SR_LOG_MAX_PREFIX 256u
+#define SR_LOG_MAX_MSGS(nbytes, n_datagrams) ((uint64_t)(nbytes) + (uint64_t)(n_datagrams))
+#define SR_LOG_TEXT_CAPACITY(nbytes, n_datagrams, prefix_max) \
+    ((uint64_t)(nbytes) * ((uint64_t)(prefix_max) + 43u) + (uint64_t)(n_datagrams) * ((uint64_t)(prefix_max) + 25u))
+
+typedef struct sr_log_batch {
+    const uint8_t *d_bytes; size_t nbytes;            /* the routed batch                                  */
+    const sr_record *d_recs; const uint64_t *d_n_records; size_t max_records;   /* input order            */
+    const uint64_t *d_hashes;                         /* NULL allowed only with min_level > 0 (TRACE)      */
+    const uint32_t *d_ends; size_t n_datagrams;       /* framed datagram ends; NULL / 0: no "got packet"   */
+    int min_level;                                    /* 0 (TRACE) or 3 (WARN)                             */
+    const uint8_t *d_prefix; uint32_t prefix_len[2];  /* TRACE bytes, then WARN bytes                      */
+    uint32_t max_msg;                                 /* 0: no cut                                         */
+    uint8_t *d_text; size_t text_cap;
+    uint32_t *d_offsets; uint8_t *d_levels; size_t max_msgs;   /* both optional                           */
+    uint64_t *d_total; uint64_t *d_n_msgs;
+} sr_log_batch;
+int sr_format_log(sr_ctx *ctx, const sr_log_batch *b);
+
+/* The log text of the host-memory path. With sr_set_logtext(ctx, min_level, text_cap, max_msg), min_level 0
+ * (TRACE) or 3 (WARN), every later sr_route_pack_submit / sr_route_pack_submit_slots / sr_route_pack_batch also
+ * formats the batch's log (sr_format_log over the batch's input-order records) into page-locked memory of the
+ * slot; a negative min_level turns the switch off (the default). The arena is sized once: text_cap bytes
+ * (0: SR_LOG_DEFAULT_TEXT_CAP(max_batch_bytes)) and an index with room for every message of a text that fits
+ * it. At TRACE the route kernel also writes the hashes, as with sr_set_trace (whose outputs stay available next
+ * to the text when it is on). Returns 0, -EINVAL (max_batch_bytes above 2^30), -EBUSY (a slot is in flight).
+ *
+ * sr_route_pack_set_prefix / sr_route_pack_set_ends stage, for the slot's NEXT submission only, the two prefixes
+ * (each at most SR_LOG_MAX_PREFIX bytes; none staged: empty) and the framed datagram ends of a
+ * sr_route_pack_submit / sr_route_pack_batch (slot 2) batch (n <= SR_MAX_SLOTS; none staged: no "got packet").
+ * Both are copied and are free for reuse on return. sr_route_pack_submit_slots takes its ends from the frame
+ * kernels instead. A max_msg that does not exceed both staged prefix lengths makes the submission return
+ * -EINVAL. Return 0, -EINVAL (switch off, bad slot or lengths), -EBUSY (the slot is in flight), -ENOMEM.
+ *
+ * sr_route_pack_logtext points at the slot's text, its total (the bytes needed), the offsets (*n_msgs + 1) and
+ * the levels (*n_msgs = the messages indexed) after sr_route_pack_result(slot), valid until the slot is
+ * submitted again (slot 2: the last sr_route_pack_batch). Returns 0 when text and index are complete, -ENOSPC
+ * when either did not fit (the caller formats that batch itself: nothing else is lost), -EINVAL, -EBUSY (the
+ * slot is in flight or was submitted with the switch off). */
+#define SR_LOG_DEFAULT_TEXT_CAP(max_batch_bytes) ((uint64_t)(max_batch_bytes) * 8u + 65536u)
+int sr_set_logtext(sr_ctx *ctx, int min_level_or_off, size_t text_cap, uint32_t max_msg);
+int sr_route_pack_set_prefix(sr_ctx *ctx, int slot, const uint8_t *trace, size_t tlen, const uint8_t *warn,
+                             size_t wlen);
+int sr_route_pack_set_ends(sr_ctx *ctx, int slot, const uint32_t *ends, size_t n);
+int sr_route_pack_logtext(sr_ctx *ctx, int slot, const uint8_t **text, uint64_t *total, const uint32_t **offsets,
+                          const uint8_t **levels, size_t *n_msgs);
+
 /* ---- owner side of the multi-GPU regroup: received lines into packets ------------------------------ */
 /* After sr_regroup_launch / sr_regroup_run the lines of the shards a GPU owns lie in d_recv_bytes /
  * d_recv_recs: every source's chunk in source order 0, 1, ..., each chunk batch 0's lines, then batch

@@ -125,6 +125,37 @@ sr_ctx *sr_core_context(sr_core *core);
  * in flight: drain first). */
 int sr_core_set_payloads(sr_core *core, int on);
 
+/* Log text from the device. With sr_core_set_device_log(core, 1, ...) every later batch also has its log
+ * messages written on the GPU (sr_set_logtext, sr_route.h: "got packet" per datagram, the WARN of every dropped
+ * line, and at log_level SR_TRACE the two find_downstream messages per routed line), at the core's log_level,
+ * into page-locked memory of the slot of text_cap bytes (0: SR_CORE_LOG_DEFAULT_TEXT_CAP of max_batch_bytes).
+ *   block == NULL: when the batch completes its messages go one by one to the log callback, as (level, text)
+ *     without prefix or newline, each cut like the host formatter's (12287 bytes): the sequence the host
+ *     formatter produces. One corner differs: for a datagram end that repeats the one before it in
+ *     sr_core_submit_datagrams' ends (an empty datagram, which by that call's contract has no entry) the host
+ *     formatter logs an empty "got packet" and the device logs none, as the reference does (sr-main.c:170).
+ *   block != NULL: prefix(user, level, dst, cap) is asked for the SR_TRACE (a TRACE core only) and the SR_WARN
+ *     prefix when the batch is submitted (it writes at most cap = SR_LOG_MAX_PREFIX bytes to dst and returns
+ *     their count); every message is prefix[level] + text cut to SR_CORE_LOG_MAX_MSG bytes (log_msg's
+ *     2048-byte buffer, sr-util.c:14-27) + '\n', and the batch's whole text goes to block(user, text, len,
+ *     n_msgs) in ONE call where its first message would have gone: after the dead downstreams' drop, before
+ *     the packets. A batch without messages makes no call.
+ * A batch whose text or index did not fit the arena, or that could not be staged (more than SR_MAX_SLOTS
+ * datagram ends in a sr_core_submit_datagrams / sr_core_route_datagrams batch), is routed as always and
+ * formatted by the host as without the switch (in block mode through the log callback), so no line is lost at
+ * any capacity or datagram count; a TRACE core keeps sr_set_trace on for that. sr_core_device_log_stats counts
+ * the completed batches whose log came from the device and those the host formatted since the core was opened
+ * (either pointer may be NULL): a host count that keeps growing says the arena is too small for the traffic. Ping lines, ERROR lines and the fault-injection paths stay host-formatted, and a batch that is taken
+ * back is formatted once, when it completes. Packets, counters and their order are the same either way. Off
+ * by default. Returns 0, -EINVAL, -EBUSY (a batch is in flight: drain first), -ENOMEM. */
+#define SR_CORE_LOG_MAX_MSG 2047u
+#define SR_CORE_LOG_DEFAULT_TEXT_CAP(max_batch_bytes) SR_LOG_DEFAULT_TEXT_CAP(max_batch_bytes)
+typedef size_t (*sr_core_log_prefix_fn)(void *user, int level, char *dst, size_t cap);
+typedef void (*sr_core_log_block_fn)(void *user, const char *text, size_t len, size_t n_msgs);
+int sr_core_set_device_log(sr_core *core, int on, size_t text_cap, sr_core_log_prefix_fn prefix,
+                           sr_core_log_block_fn block);
+int sr_core_device_log_stats(const sr_core *core, uint64_t *device_batches, uint64_t *host_batches);
+
 /* Test hook (fault injection; nothing calls it in the executable): the fail_submit-th call of
  * sr_core_submit* fails as a failed sr_route_pack_submit (the batch is not taken), and the
  * fail_finish-th batch to complete fails as a failed sr_route_pack_result (its packets and log lines

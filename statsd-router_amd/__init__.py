@@ -58,7 +58,25 @@ ABI_FUNCTIONS = (
     "sr_exchange_dead_run", "sr_exchange_dead", "sr_owner_pack", "sr_flush_pending",
     "sr_comm_group_open", "sr_comm_group_close", "sr_comm_open_local", "sr_comm_set_timeout", "sr_comm_transport",
     "sr_frame_slots_size", "sr_frame_slots", "sr_route_pack_submit_slots",
+    "sr_format_log", "sr_set_logtext", "sr_route_pack_set_prefix", "sr_route_pack_set_ends", "sr_route_pack_logtext",
 )
+SR_LOG_MAX_PREFIX = 256
+SR_LOG_TRACE, SR_LOG_WARN = 0, 3   # sr_log_batch.min_level and the d_levels values
+
+
+def log_default_text_cap(max_batch_bytes: int) -> int:
+    """SR_LOG_DEFAULT_TEXT_CAP: the slots' text arena when sr_set_logtext is given 0."""
+    return max_batch_bytes * 8 + 65536
+
+
+def log_max_msgs(nbytes: int, n_datagrams: int) -> int:
+    """SR_LOG_MAX_MSGS: index room that always suffices."""
+    return nbytes + n_datagrams
+
+
+def log_text_capacity(nbytes: int, n_datagrams: int, prefix_max: int) -> int:
+    """SR_LOG_TEXT_CAPACITY: text room that always suffices (the worst case is a batch of one-byte lines)."""
+    return nbytes * (prefix_max + 43) + n_datagrams * (prefix_max + 25)
 SR_MAX_SLOTS = 65536
 SR_MAX_SLOT_STRIDE = 1 << 27
 SR_MAX_PACK_DOWNSTREAMS = 4096
@@ -127,6 +145,17 @@ class SrSlotBatch(ctypes.Structure):
     _fields_ = [("d_slots", ctypes.c_void_p), ("stride", ctypes.c_size_t), ("d_lens", ctypes.c_void_p),
                 ("count", ctypes.c_size_t), ("d_bytes", ctypes.c_void_p), ("cap", ctypes.c_size_t),
                 ("d_ends", ctypes.c_void_p), ("d_total", ctypes.c_void_p)]
+
+
+class SrLogBatch(ctypes.Structure):
+    """struct sr_log_batch (include/sr_route.h): one batch of sr_format_log."""
+    _fields_ = [("d_bytes", ctypes.c_void_p), ("nbytes", ctypes.c_size_t), ("d_recs", ctypes.c_void_p),
+                ("d_n_records", ctypes.c_void_p), ("max_records", ctypes.c_size_t), ("d_hashes", ctypes.c_void_p),
+                ("d_ends", ctypes.c_void_p), ("n_datagrams", ctypes.c_size_t), ("min_level", ctypes.c_int),
+                ("d_prefix", ctypes.c_void_p), ("prefix_len", ctypes.c_uint32 * 2), ("max_msg", ctypes.c_uint32),
+                ("d_text", ctypes.c_void_p), ("text_cap", ctypes.c_size_t), ("d_offsets", ctypes.c_void_p),
+                ("d_levels", ctypes.c_void_p), ("max_msgs", ctypes.c_size_t), ("d_total", ctypes.c_void_p),
+                ("d_n_msgs", ctypes.c_void_p)]
 
 
 class SrOwnerBatch(ctypes.Structure):
@@ -276,6 +305,12 @@ def _load_route_lib() -> ctypes.CDLL:
         "sr_frame_slots_size": (ctypes.c_size_t, [vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]),
         "sr_frame_slots": (ctypes.c_int, [vp, ctypes.POINTER(SrSlotBatch)]),
         "sr_route_pack_submit_slots": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_size_t, vp, ctypes.c_size_t, vp]),
+        "sr_format_log": (ctypes.c_int, [vp, ctypes.POINTER(SrLogBatch)]),
+        "sr_set_logtext": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_size_t, ctypes.c_uint32]),
+        "sr_route_pack_set_prefix": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_size_t, vp, ctypes.c_size_t]),
+        "sr_route_pack_set_ends": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_size_t]),
+        "sr_route_pack_logtext": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(vp), u64p, ctypes.POINTER(vp),
+                                                 ctypes.POINTER(vp), c_size_p]),
     }
     for name in ABI_FUNCTIONS:
         if os.environ.get("SR_ROUTE_LIB") and not hasattr(lib, name):
@@ -619,6 +654,48 @@ class Router:
         b = SrSlotBatch(d_slots or None, stride, d_lens or None, count, d_bytes or None, cap, d_ends or None,
                         d_total or None)
         _check(self._lib.sr_frame_slots(self._h, ctypes.byref(b)), "sr_frame_slots")
+
+    def set_logtext(self, min_level: int | None, text_cap: int = 0, max_msg: int = 0) -> None:
+        """sr_set_logtext: later route_pack submissions also format the batch's log text at min_level
+        (SR_LOG_TRACE or SR_LOG_WARN); None turns it off."""
+        _check(self._lib.sr_set_logtext(self._h, -1 if min_level is None else min_level, text_cap, max_msg),
+               "sr_set_logtext")
+        self._log_cap = text_cap or log_default_text_cap(self.max_batch_bytes)
+
+    def route_pack_set_prefix(self, slot: int, trace: bytes = b"", warn: bytes = b"") -> None:
+        """sr_route_pack_set_prefix: the TRACE and WARN prefixes of the slot's next submission."""
+        _check(self._lib.sr_route_pack_set_prefix(self._h, slot, trace or None, len(trace), warn or None, len(warn)),
+               "sr_route_pack_set_prefix")
+
+    def route_pack_set_ends(self, slot: int, ends) -> None:
+        """sr_route_pack_set_ends: the framed datagram ends of the slot's next submission."""
+        e = np.ascontiguousarray(ends, dtype=np.uint32)
+        _check(self._lib.sr_route_pack_set_ends(self._h, slot, e.ctypes.data if e.size else None, int(e.size)),
+               "sr_route_pack_set_ends")
+
+    def route_pack_logtext(self, slot: int):
+        """sr_route_pack_logtext after route_pack_result(slot): (text bytes, total, offsets, levels, complete),
+        copied out of the slot; text holds min(total, the arena's size) bytes when incomplete."""
+        text, offs, lv = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        total, n = ctypes.c_uint64(), ctypes.c_size_t()
+        rc = self._lib.sr_route_pack_logtext(self._h, slot, ctypes.byref(text), ctypes.byref(total), ctypes.byref(offs),
+                                             ctypes.byref(lv), ctypes.byref(n))
+        if rc != -errno.ENOSPC:
+            _check(rc, "sr_route_pack_logtext")
+        k = n.value
+        offsets = np.frombuffer(ctypes.string_at(offs.value, 4 * (k + 1)), dtype=np.uint32).copy()
+        levels = np.frombuffer(ctypes.string_at(lv.value, k), dtype=np.uint8).copy()
+        return ctypes.string_at(text.value, min(total.value, self._log_cap)), total.value, offsets, levels, rc == 0
+
+    def format_log(self, batch: SrLogBatch | None = None, **fields) -> None:
+        """sr_format_log with raw device pointers (0 / None = NULL): a routed batch's log text written on the
+        device, asynchronous on the context's stream. Fields as struct sr_log_batch; prefix_len is a pair
+        (TRACE bytes, WARN bytes). Tensors pass their data_ptr()."""
+        if batch is None:
+            plen = fields.pop("prefix_len", (0, 0))
+            batch = SrLogBatch(**{k: (v or None) if k.startswith("d_") else v for k, v in fields.items()})
+            batch.prefix_len[0], batch.prefix_len[1] = int(plen[0]), int(plen[1])
+        _check(self._lib.sr_format_log(self._h, ctypes.byref(batch)), "sr_format_log")
 
     def route_pack_submit_slots(self, slot: int, slots, stride: int, lens, fill=None) -> None:
         """sr_route_pack_submit_slots (asynchronous): `slots` is page-locked memory (a HostBuffer, or its

@@ -30,6 +30,9 @@ class CoreConfig(ctypes.Structure):
 EMIT_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(IoVec), ctypes.c_int, ctypes.c_size_t)
 LOG_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t)
 FLUSH_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p)
+LOG_PREFIX_FN = ctypes.CFUNCTYPE(ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t)
+LOG_BLOCK_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t)
+LOG_BLOCK = -1   # the level of a block entry in Core.logs
 
 _RLIB = None
 
@@ -71,6 +74,10 @@ def router_lib() -> ctypes.CDLL:
         L.sr_core_set_payloads.restype, L.sr_core_set_payloads.argtypes = ctypes.c_int, [vp, ctypes.c_int]
         L.sr_core_submit_slots.restype = ctypes.c_int
         L.sr_core_submit_slots.argtypes = [vp, ctypes.c_int, vp, ctypes.c_size_t]
+        L.sr_core_set_device_log.restype = ctypes.c_int
+        L.sr_core_set_device_log.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, LOG_PREFIX_FN, LOG_BLOCK_FN]
+        L.sr_core_device_log_stats.restype = ctypes.c_int
+        L.sr_core_device_log_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         _RLIB = L
     return _RLIB
 
@@ -192,6 +199,33 @@ class Core:
         """sr_core_set_payloads: later batches' packets come from the device's arena (at most two pieces
         per emitted packet)."""
         _check(self._L.sr_core_set_payloads(self._h, 1 if on else 0), "sr_core_set_payloads")
+
+    def set_device_log(self, on: bool = True, text_cap: int = 0, prefixes=None) -> None:
+        """sr_core_set_device_log. prefixes None: per-message mode (the messages reach `logs` as always).
+        prefixes = (TRACE bytes, WARN bytes): block mode; every batch's text is recorded as one
+        (LOG_BLOCK, text) entry of `logs`, in its place among the host's messages, and as (text, n_msgs) in
+        `blocks`."""
+        self.blocks = getattr(self, "blocks", [])
+
+        def prefix(_u, level, dst, cap):
+            p = prefixes[1 if level >= SR_WARN else 0][:cap]
+            ctypes.memmove(dst, p, len(p))
+            return len(p)
+
+        def block(_u, text, n, n_msgs):
+            b = ctypes.string_at(text, n)
+            self.blocks.append((b, int(n_msgs)))
+            self.logs.append((LOG_BLOCK, b))
+
+        blk = on and prefixes is not None
+        self._log_cb = (LOG_PREFIX_FN(prefix) if blk else LOG_PREFIX_FN(0), LOG_BLOCK_FN(block) if blk else LOG_BLOCK_FN(0))
+        _check(self._L.sr_core_set_device_log(self._h, 1 if on else 0, text_cap, *self._log_cb), "sr_core_set_device_log")
+
+    def device_log_stats(self):
+        """sr_core_device_log_stats: (batches whose log came from the device, batches the host formatted)."""
+        d, h = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self._L.sr_core_device_log_stats(self._h, ctypes.byref(d), ctypes.byref(h)), "sr_core_device_log_stats")
+        return d.value, h.value
 
     def set_layout(self, layout: int) -> None:
         """sr_set_layout on the core's device context (sr_core_context)."""

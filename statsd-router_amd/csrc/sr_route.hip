@@ -20,6 +20,7 @@
 #include "frame_host.hpp"
 #include "frame_kernel.hpp"
 #include "local_comm.hpp"
+#include "log_kernel.hpp"
 #include "mtu_kernel.hpp"
 #include "owner_kernel.hpp"
 #include "payload_kernel.hpp"
@@ -70,8 +71,14 @@ struct sr_ctx {
     uint64_t *d_owner_n;
     uint16_t *d_owner_fill;       // [nds]
     uint32_t *d_frame;            // sr_frame_slots: kFrameMaxGroups sums | SR_MAX_SLOTS workgroup-local ends
+    uint64_t *d_log;              // sr_format_log: {bytes, messages} per kLogRecs records of a full batch
     int trace;                    // sr_set_trace: submissions also return input-order records + hashes
     int payloads;                 // sr_set_payloads: submissions also return the packets' bytes
+    // sr_set_logtext: submissions also return the batch's log text (log_level < 0: off)
+    int logtext, log_level;
+    size_t log_cap, log_msgs;     // the slots' text bytes and index entries
+    uint32_t log_max_msg;
+    uint32_t *d_ends;             // slot submissions at TRACE: the frame kernels' datagram ends (SR_MAX_SLOTS)
     // packing knobs (sr_set_knob): forced chunk lines (0: by shape), XCD-local chunks, chain walked in emit
     uint32_t mtu_chunk;
     int mtu_xcd, mtu_walk;
@@ -100,6 +107,12 @@ struct sr_ctx {
         uint8_t *phost, *pdev;
         size_t pay_cap, poff_cap; // arena bytes; offsets - 1 (descriptors)
         int payloaded;            // the batch in the slot was submitted with payloads on
+        // sr_set_logtext: text | offsets | levels | {total, messages} | staged prefixes | staged ends
+        uint8_t *lhost, *ldev;
+        size_t ltext_cap, lmsg_cap;
+        uint32_t stage_plen[2];   // sr_route_pack_set_prefix, for the next submission
+        size_t stage_ends;        // sr_route_pack_set_ends, for the next submission
+        int logged;               // the batch in the slot was submitted with the log text on
     } slot[3];
 };
 
@@ -218,10 +231,13 @@ void sr_close(sr_ctx *c) {
     free_ptr(c->d_owner_n);
     free_ptr(c->d_owner_fill);
     free_ptr(c->d_frame);
+    free_ptr(c->d_log);
+    free_ptr(c->d_ends);
     for (auto &sl : c->slot) {
         if (sl.host) (void)hipHostFree(sl.host);
         if (sl.thost) (void)hipHostFree(sl.thost);
         if (sl.phost) (void)hipHostFree(sl.phost);
+        if (sl.lhost) (void)hipHostFree(sl.lhost);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -910,6 +926,59 @@ static int frame_impl(sr_ctx *c, const sr_slot_batch *b) {
 
 int sr_frame_slots(sr_ctx *c, const sr_slot_batch *b) { return frame_impl(c, b); }
 
+// The three formatting launches on the context's stream (log_kernel.hpp). The scratch is allocated once, for a
+// batch of max_batch_bytes one-byte lines, by the first call: later calls allocate nothing and can be captured
+// in a graph.
+static int log_impl(sr_ctx *c, const sr_log_batch *b) {
+    static_assert(SR_LOG_MAX_PREFIX == kLogMaxPrefix, "prefix room in LDS");
+    if (!c || !b || !b->d_total || !b->d_n_msgs || !b->d_n_records) return -EINVAL;
+    if (b->min_level < 0 || b->min_level > 3) return -EINVAL;
+    if (b->nbytes > c->ds.max_batch || b->nbytes > kLogMaxBatch || (b->nbytes && !b->d_bytes)) return -EINVAL;
+    const size_t rec_room = b->max_records < b->nbytes ? b->max_records : b->nbytes;   // a line has a byte
+    if (rec_room && (!b->d_recs || (b->min_level == 0 && !b->d_hashes))) return -EINVAL;
+    if (b->d_ends && b->n_datagrams > 0xFFFFFFF0ull) return -EINVAL;
+    if (b->prefix_len[0] > kLogMaxPrefix || b->prefix_len[1] > kLogMaxPrefix) return -EINVAL;
+    if ((b->prefix_len[0] || b->prefix_len[1]) && !b->d_prefix) return -EINVAL;
+    if (b->max_msg && (b->max_msg <= b->prefix_len[0] || b->max_msg <= b->prefix_len[1])) return -EINVAL;
+    if (b->text_cap && !b->d_text) return -EINVAL;
+    (void)hipSetDevice(c->device);
+    const size_t full = c->ds.max_batch < kLogMaxBatch ? c->ds.max_batch : kLogMaxBatch;
+    if (!c->d_log && hipMalloc(&c->d_log, 2 * ((full + kLogRecs - 1) / kLogRecs + 1) * sizeof(uint64_t)) != hipSuccess) {
+        c->d_log = nullptr;
+        return -ENOMEM;
+    }
+    LogArgs a;
+    a.bytes = b->d_bytes;
+    a.recs = b->d_recs;
+    a.n_records = b->d_n_records;
+    a.hashes = b->d_hashes;
+    a.ends = b->d_ends;
+    a.prefix = b->d_prefix;
+    a.text = b->d_text;
+    a.offsets = b->d_offsets;
+    a.levels = b->d_levels;
+    a.total = b->d_total;
+    a.n_msgs = b->d_n_msgs;
+    a.gsum = c->d_log;
+    a.text_cap = b->text_cap;
+    a.max_msgs = b->max_msgs;
+    a.nbytes = (uint32_t)b->nbytes;
+    a.rec_room = (uint32_t)rec_room;
+    a.n_ends = b->d_ends ? (uint32_t)b->n_datagrams : 0u;
+    a.nds = c->ds.nds;
+    a.plen[0] = b->prefix_len[0];
+    a.plen[1] = b->prefix_len[1];
+    a.max_msg = b->max_msg;
+    a.warn_only = b->min_level > 0 ? 1u : 0u;
+    const uint32_t groups = (a.rec_room + (uint32_t)kLogRecs - 1u) / (uint32_t)kLogRecs;
+    if (groups) hipLaunchKernelGGL(log_lens_kernel, dim3(groups), dim3(kLogRecs), 0, c->stream, a);
+    hipLaunchKernelGGL(log_scan_kernel, dim3(1), dim3(1024), 0, c->stream, a);
+    if (groups) hipLaunchKernelGGL(log_write_kernel, dim3(groups), dim3(kLogRecs), 0, c->stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+int sr_format_log(sr_ctx *c, const sr_log_batch *b) { return log_impl(c, b); }
+
 static int grow(void **ptr, size_t *cap, size_t need, size_t elem) {
     if (need <= *cap) return 0;
     free_ptr(*ptr);
@@ -1003,6 +1072,43 @@ static int slot_payload_reserve(sr_ctx *c, int k, size_t nbytes) {
     return 0;
 }
 
+// sr_set_logtext: the slot's text arena, index, totals and the staging of prefixes and ends (sized by the
+// switch, which only changes while every slot is idle)
+struct LogLayout {
+    size_t o_off, o_lv, o_tot, o_pfx, o_ends, total;
+};
+static LogLayout log_layout(size_t text_cap, size_t msgs) {
+    LogLayout l;
+    l.o_off = up256(text_cap);
+    l.o_lv = l.o_off + up256((msgs + 1) * sizeof(uint32_t));
+    l.o_tot = l.o_lv + up256(msgs);
+    l.o_pfx = l.o_tot + 256;
+    l.o_ends = l.o_pfx + up256(2 * (size_t)kLogMaxPrefix);
+    l.total = l.o_ends + up256((size_t)SR_MAX_SLOTS * sizeof(uint32_t));
+    return l;
+}
+static int slot_log_reserve(sr_ctx *c, int k) {
+    sr_ctx::Slot &sl = c->slot[k];
+    if (sl.lhost && sl.ltext_cap == c->log_cap && sl.lmsg_cap == c->log_msgs) return 0;
+    if (sl.lhost) (void)hipHostFree(sl.lhost);
+    sl.lhost = sl.ldev = nullptr;
+    sl.ltext_cap = sl.lmsg_cap = 0;
+    sl.stage_plen[0] = sl.stage_plen[1] = 0;
+    sl.stage_ends = 0;
+    sl.logged = 0;
+    void *h = nullptr, *d = nullptr;
+    if (hipHostMalloc(&h, log_layout(c->log_cap, c->log_msgs).total, hipHostMallocMapped) != hipSuccess) return -ENOMEM;
+    if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
+        (void)hipHostFree(h);
+        return -EIO;
+    }
+    sl.lhost = (uint8_t *)h;
+    sl.ldev = (uint8_t *)d;
+    sl.ltext_cap = c->log_cap;
+    sl.lmsg_cap = c->log_msgs;
+    return 0;
+}
+
 // The datagrams of a slot submission (sr_route_pack_submit_slots): framed on the device into c->d_in.
 struct SlotSource {
     const uint8_t *d_slots;   // the device address of the caller's page-locked slots
@@ -1020,6 +1126,9 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
     if ((nbytes && !bytes && !src) || nbytes > c->ds.max_batch) return -EINVAL;
     if (c->ds.nds > SR_MAX_PACK_DOWNSTREAMS) return -EINVAL;
     if (!src && nbytes && bytes[nbytes - 1] != '\n') return -EINVAL;
+    if (c->logtext && c->log_max_msg && sl.lhost &&
+        (c->log_max_msg <= sl.stage_plen[0] || c->log_max_msg <= sl.stage_plen[1]))
+        return -EINVAL;   // sr_format_log would refuse it after the route was enqueued
     (void)hipSetDevice(c->device);
     const size_t nds = c->ds.nds, nw = c->ds.nwords;
     int rc;
@@ -1030,6 +1139,12 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
     if ((rc = slot_reserve(c, k, full))) return rc;
     if (c->trace && (rc = slot_trace_reserve(c, k, full))) return rc;
     if (c->payloads && (rc = slot_payload_reserve(c, k, full))) return rc;
+    if (c->logtext && (rc = slot_log_reserve(c, k))) return rc;
+    const bool log_trace = c->logtext && c->log_level == 0;   // the formatter needs hashes and datagram ends
+    if (log_trace && src && !c->d_ends && hipMalloc(&c->d_ends, (size_t)SR_MAX_SLOTS * sizeof(uint32_t)) != hipSuccess) {
+        c->d_ends = nullptr;
+        return -ENOMEM;
+    }
     const size_t cap = nbytes ? nbytes : 1;   // never more lines than bytes
     const size_t pcap = (size_t)SR_MAX_PACKETS(cap, nds);
     if ((rc = grow((void **)&c->d_out, &c->d_out_cap, full, sizeof(sr_record)))) return rc;
@@ -1059,7 +1174,7 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
         if (src) {   // the lengths staged like the fill; the datagrams read in place, no bulk copy
             memcpy(sl.lens_in, src->lens, src->count * sizeof(uint16_t));
             const sr_slot_batch fb{src->d_slots, src->stride, (const uint16_t *)(sl.dev + ((uint8_t *)sl.lens_in - sl.host)),
-                                   src->count, c->d_in, c->ds.max_batch, nullptr,
+                                   src->count, c->d_in, c->ds.max_batch, log_trace ? c->d_ends : nullptr,
                                    (uint64_t *)(sl.dev + ((uint8_t *)(sl.counts + 3) - sl.host))};
             if ((rc = frame_impl(c, &fb))) return rc;
         } else if (hipMemcpyAsync(c->d_in, bytes, nbytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
@@ -1070,7 +1185,7 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
         // up to 1024 the probes note the dead shards themselves
         // TRACE (sr_set_trace) needs every line's hash too (sr-main.c:91)
         uint64_t *hashes = nullptr;
-        if (c->trace || c->ds.replay_wants_hashes()) {
+        if (c->trace || log_trace || c->ds.replay_wants_hashes()) {
             if ((rc = grow((void **)&c->d_hash, &c->d_hash_cap, full, sizeof(uint64_t)))) return rc;
             hashes = c->d_hash;
         }
@@ -1114,6 +1229,29 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
                                   c->d_mcounts, f_out, nullptr, nullptr, sl.pdev, sl.pay_cap,
                                   (uint32_t *)(sl.pdev + o_off), (uint64_t *)(sl.pdev + o_tot)};
         if ((rc = payloads_impl(c, &yb, 1))) return rc;
+    }
+    sl.logged = 0;
+    if (c->logtext) {   // the batch's log text straight into the slot's page-locked memory (log_kernel.hpp)
+        const LogLayout l = log_layout(sl.ltext_cap, sl.lmsg_cap);
+        const uint32_t *ends = nullptr;
+        size_t n_ends = 0;
+        if (log_trace && nbytes) {
+            if (src) {
+                ends = c->d_ends;
+                n_ends = src->count;
+            } else if (sl.stage_ends) {
+                ends = (const uint32_t *)(sl.ldev + l.o_ends);
+                n_ends = sl.stage_ends;
+            }
+        }
+        const sr_log_batch lb{c->d_in, nbytes, c->d_out, c->d_count, nbytes ? cap : 0, log_trace && nbytes ? c->d_hash : nullptr,
+                              ends, n_ends, c->log_level, sl.ldev + l.o_pfx, {sl.stage_plen[0], sl.stage_plen[1]},
+                              c->log_max_msg, sl.ldev, sl.ltext_cap, (uint32_t *)(sl.ldev + l.o_off), sl.ldev + l.o_lv,
+                              sl.lmsg_cap, (uint64_t *)(sl.ldev + l.o_tot), (uint64_t *)(sl.ldev + l.o_tot) + 1};
+        if ((rc = log_impl(c, &lb))) return rc;
+        sl.logged = 1;
+        sl.stage_plen[0] = sl.stage_plen[1] = 0;   // staged for one submission
+        sl.stage_ends = 0;
     }
     if (hipEventRecord(sl.done, c->stream) != hipSuccess) return -EIO;
     sl.busy = 1;
@@ -1160,6 +1298,72 @@ int sr_route_pack_payloads(sr_ctx *c, int slot, const uint8_t **payload, const u
     *payload = sl.phost;
     *offsets = (const uint32_t *)(sl.phost + up256(sl.pay_cap));
     return 0;
+}
+
+int sr_set_logtext(sr_ctx *c, int min_level_or_off, size_t text_cap, uint32_t max_msg) {
+    if (!c || min_level_or_off > 3) return -EINVAL;
+    for (int k = 0; k < 3; ++k)
+        if (c->slot[k].busy) return -EBUSY;
+    if (min_level_or_off < 0) {
+        c->logtext = 0;
+        return 0;
+    }
+    if (c->ds.max_batch > kLogMaxBatch) return -EINVAL;
+    const size_t cap = text_cap ? text_cap : (size_t)SR_LOG_DEFAULT_TEXT_CAP(c->ds.max_batch);
+    // a message is at least its header (24 bytes or more) or max_msg bytes, and its '\n': a text that fits
+    // the arena has no more messages than this, so its index fits too
+    const size_t least = (max_msg && max_msg < 24u ? max_msg : 24u) + 1u;
+    const uint64_t most = SR_LOG_MAX_MSGS(c->ds.max_batch, SR_MAX_SLOTS);
+    const uint64_t msgs = (uint64_t)cap / least + 1u;
+    c->logtext = 1;
+    c->log_level = min_level_or_off;
+    c->log_cap = cap;
+    c->log_msgs = (size_t)(msgs < most ? msgs : most);
+    c->log_max_msg = max_msg;
+    return 0;
+}
+
+int sr_route_pack_set_prefix(sr_ctx *c, int slot, const uint8_t *trace, size_t tlen, const uint8_t *warn, size_t wlen) {
+    if (!c || slot < 0 || slot > 2 || !c->logtext) return -EINVAL;
+    if (tlen > kLogMaxPrefix || wlen > kLogMaxPrefix || (tlen && !trace) || (wlen && !warn)) return -EINVAL;
+    sr_ctx::Slot &sl = c->slot[slot];
+    if (sl.busy) return -EBUSY;
+    (void)hipSetDevice(c->device);
+    int rc = slot_log_reserve(c, slot);
+    if (rc) return rc;
+    uint8_t *const p = sl.lhost + log_layout(sl.ltext_cap, sl.lmsg_cap).o_pfx;
+    if (tlen) memcpy(p, trace, tlen);
+    if (wlen) memcpy(p + tlen, warn, wlen);
+    sl.stage_plen[0] = (uint32_t)tlen;
+    sl.stage_plen[1] = (uint32_t)wlen;
+    return 0;
+}
+
+int sr_route_pack_set_ends(sr_ctx *c, int slot, const uint32_t *ends, size_t n) {
+    if (!c || slot < 0 || slot > 2 || !c->logtext || n > SR_MAX_SLOTS || (n && !ends)) return -EINVAL;
+    sr_ctx::Slot &sl = c->slot[slot];
+    if (sl.busy) return -EBUSY;
+    (void)hipSetDevice(c->device);
+    int rc = slot_log_reserve(c, slot);
+    if (rc) return rc;
+    if (n) memcpy(sl.lhost + log_layout(sl.ltext_cap, sl.lmsg_cap).o_ends, ends, n * sizeof(uint32_t));
+    sl.stage_ends = n;
+    return 0;
+}
+
+int sr_route_pack_logtext(sr_ctx *c, int slot, const uint8_t **text, uint64_t *total, const uint32_t **offsets,
+                          const uint8_t **levels, size_t *n_msgs) {
+    if (!c || !text || !total || !offsets || !levels || !n_msgs || slot < 0 || slot > 2) return -EINVAL;
+    const sr_ctx::Slot &sl = c->slot[slot];
+    if (sl.busy || !sl.logged || !sl.lhost) return -EBUSY;
+    const LogLayout l = log_layout(sl.ltext_cap, sl.lmsg_cap);
+    const uint64_t *tot = (const uint64_t *)(sl.lhost + l.o_tot);
+    *text = sl.lhost;
+    *total = tot[0];
+    *offsets = (const uint32_t *)(sl.lhost + l.o_off);
+    *levels = sl.lhost + l.o_lv;
+    *n_msgs = (size_t)(tot[1] < sl.lmsg_cap ? tot[1] : sl.lmsg_cap);
+    return (tot[0] > sl.ltext_cap || tot[1] > sl.lmsg_cap) ? -ENOSPC : 0;
 }
 
 int sr_route_pack_submit(sr_ctx *c, int slot, const uint8_t *bytes, size_t nbytes, const uint16_t *fill) {
