@@ -620,6 +620,21 @@ int sr_core_device_log_stats(const sr_core *c, uint64_t *device_batches, uint64_
     return 0;
 }
 
+int sr_core_set_name_stats(sr_core *c, const sr_stats_config *cfg) {
+    if (!c) return -EINVAL;
+    if (c->in_flight >= 0) return -EBUSY;
+    return sr_set_name_stats(c->ctx, cfg);
+}
+
+int sr_core_name_stats(sr_core *c, sr_stats_snapshot **out, int reset) {
+    if (out) *out = NULL;
+    if (!c || !out) return -EINVAL;
+    int rc = sr_core_drain(c);
+    if (rc) return rc;
+    if ((rc = sr_stats_read(c->ctx, out))) return rc;
+    return reset ? sr_stats_reset(c->ctx) : 0;
+}
+
 int sr_core_inject_faults(sr_core *c, unsigned fail_submit, unsigned fail_finish) {
     if (!c) return -EINVAL;
     c->fail_submit = fail_submit;

@@ -61,6 +61,8 @@ typedef struct sr_config {
                                                 /* are framed on the GPU (sr_core_submit_slots); off by default    */
     int dt_device_log;                          /* SR_DEVICE_LOG=1: a batch's log text is written on the GPU and goes */
                                                 /* to stdout in one write (sr_core_set_device_log); off by default   */
+    int dt_name_stats;                          /* SR_NAME_STATS=1: data lines are counted on the GPU and every ping  */
+                                                /* tick logs the hot names (sr_core_set_name_stats); off by default  */
     int dt_yield;                               /* full batches per read event before timers run (0: no cap) */
     double dt_yield_s;                          /* seconds per read event before timers run (0: no cap)  */
     /* alive bits published by the health checker to the data threads */

@@ -287,6 +287,29 @@ static void flush_timer_cb(struct ev_loop *loop, ev_periodic *p, int revents) {
     sr_core_flush_timer(d->core);
 }
 
+/* SR_NAME_STATS=1: what the thread routed since its last ping, then the statistics start again. A thread that
+ * routed no valid line logs nothing. */
+#define NAME_STATS_HOT_LINES 8
+static void log_name_stats(data_thread *d) {
+    sr_stats_snapshot *s = NULL;
+    int rc = sr_core_name_stats(d->core, &s, 1);
+    if (rc) {
+        sr_log(SR_ERROR, "%s: sr_core_name_stats() failed %s", "ping_cb", strerror(-rc));
+        return;
+    }
+    if (s->lines[SR_VALID]) {
+        sr_log(SR_INFO, "name_stats: lines=%llu names~%llu hot=%u%s", (unsigned long long)s->lines[SR_VALID],
+               (unsigned long long)(sr_stats_cardinality(s, SR_STATS_ALL) + 0.5), s->n_hot, s->hot_overflow ? "+" : "");
+        for (uint32_t i = 0; i < s->n_hot && i < NAME_STATS_HOT_LINES; i++) {
+            const sr_stats_hot *h = &s->hot[i];
+            sr_log(SR_INFO, "name_stats: hot %.*s lines~%llu",
+                   (int)(h->name_len < SR_STATS_NAME_MAX ? h->name_len : SR_STATS_NAME_MAX), (const char *)h->name,
+                   (unsigned long long)h->lines);
+        }
+    }
+    sr_stats_free(s);
+}
+
 static void ping_timer_cb(struct ev_loop *loop, ev_periodic *p, int revents) {
     (void)loop, (void)revents;
     data_thread *d = (data_thread *)((char *)p - offsetof(data_thread, ping_timer));
@@ -294,6 +317,7 @@ static void ping_timer_cb(struct ev_loop *loop, ev_periodic *p, int revents) {
     refresh_alive(d);
     int rc = sr_core_ping(d->core);
     if (rc) sr_log(SR_ERROR, "%s: sr_core_ping() failed %s", "ping_cb", strerror(-rc));
+    if (d->c->dt_name_stats) log_name_stats(d);
 }
 
 /* a data thread that cannot route: the process ends (status 1) unless SR_REQUIRE_GPU=0 */
@@ -359,6 +383,13 @@ void *sr_data_thread(void *arg) {
     if (c->dt_device_log && (rc = sr_core_set_device_log(d->core, 1, 0, on_log_prefix, on_log_block))) {
         sr_log(SR_ERROR, "%s: sr_core_set_device_log() failed %s", fn, strerror(-rc));
         return thread_fail(d, 1);
+    }
+    if (c->dt_name_stats) {
+        const sr_stats_config defaults = {0, 0, 0, 0, 0, 0};
+        if ((rc = sr_core_set_name_stats(d->core, &defaults))) {
+            sr_log(SR_ERROR, "%s: sr_core_set_name_stats() failed %s", fn, strerror(-rc));
+            return thread_fail(d, 1);
+        }
     }
     d->slot = 0;
     d->batch = sr_core_slot_buffer(d->core, 0, &d->cap);
@@ -436,6 +467,8 @@ int main(int argc, char *argv[]) {
     config.dt_device_framing = df && df[0] == '1';
     const char *dl = getenv("SR_DEVICE_LOG");
     config.dt_device_log = dl && dl[0] == '1';
+    const char *ns = getenv("SR_NAME_STATS");
+    config.dt_name_stats = ns && ns[0] == '1';
     config.dt_yield = dy ? atoi(dy) : 0;
     config.dt_yield_s = dys ? atof(dys) : READ_EVENT_SECONDS;
 

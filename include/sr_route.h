@@ -689,6 +689,130 @@ int sr_route_pack_set_ends(sr_ctx *ctx, int slot, const uint32_t *ends, size_t n
 int sr_route_pack_logtext(sr_ctx *ctx, int slot, const uint8_t **text, uint64_t *total, const uint32_t **offsets,
                           const uint8_t **levels, size_t *n_msgs);
 
+/* ---- name statistics on the device: hot names and distinct names per shard ---------------------------- */
+/* The shard of a line is a pure function of its name, so one hot name is one overloaded downstream. This stage
+ * consumes what the route launch leaves on the device (the input-order records and the 64-bit name hashes) and
+ * keeps, per context, sketches that answer "which names carry the traffic" and "how many distinct names does
+ * shard k hold". Everything is exact and deterministic (tests/stats_expect.py restates it in numpy).
+ *
+ * State, from sr_stats_open or the last sr_stats_reset:
+ *   lines[4], bytes[4]        per verdict (sr_record_verdict): the records seen and the sum of their `length`;
+ *   ignored                   records whose route is neither below n_downstreams nor an SR_ROUTE_* code; they
+ *                             touch nothing else;
+ *   shard_lines[n], shard_bytes[n]   the same sums per shard over the valid lines; total = lines[SR_VALID].
+ * Per valid record with name hash h, m = fmix64(h) (the MurmurHash3 finaliser: m ^= m >> 33; m *=
+ * 0xff51afd7ed558ccd; m ^= m >> 33; m *= 0xc4ceb9fe1a85ec53; m ^= m >> 33):
+ *   distinct names (HyperLogLog, 2^p u8 registers per shard): idx = m >> (64 - p), w = m << p,
+ *     rho = w == 0 ? 64 - p + 1 : clz64(w) + 1, reg[shard][idx] = max(reg, rho);
+ *   lines per name (count-min sketch, D rows of W u64 cells, one per context): a = (u32)m, b = (u32)(m >> 32) | 1,
+ *     row r adds 1 to cell (a + r * b) & (W - 1) (32-bit wrapping); est(h) = the minimum over the rows. It never
+ *     underestimates; overestimates (colliding cells) are part of the contract;
+ *   hot names, settled after every record of the call is counted: T = max(hot_min_lines, ceil(total / hot_div));
+ *     every valid record of this call with est(h) >= T puts its name into the hot table (hot_slots entries)
+ *     unless it is there; a name stays until reset; one that finds no room sets hot_overflow. Equal hashes are
+ *     equal names: which line supplies the bytes is not specified.
+ * The name is the line's bytes before its first ':' inside the line clipped to [0, nbytes) (a record without a
+ * ':' there: the whole clipped run); name_len is its full length, the first min(name_len, SR_STATS_NAME_MAX)
+ * bytes are stored, the rest of `name` is zero. Only min(*d_n_records, max_records) records of a batch are
+ * read, and no byte outside [0, nbytes).
+ *
+ * sr_stats_config: all six zero selects the defaults below. Limits: hll_p in SR_STATS_MIN_P..SR_STATS_MAX_P
+ *   with n_downstreams << hll_p at most SR_STATS_MAX_REGS; cms_rows in 1..SR_STATS_MAX_ROWS; cms_width a power
+ *   of two, at least SR_STATS_MIN_WIDTH, with cms_rows * cms_width <= SR_STATS_MAX_CELLS (a workgroup keeps the
+ *   whole sketch in LDS as u32: 64 KiB); hot_slots a power of two in SR_STATS_MIN_SLOTS..SR_STATS_MAX_SLOTS;
+ *   hot_div >= 1.
+ * sr_stats_open  : allocates everything, once (not inside stream capture). 0, -EINVAL, -ENOMEM, -EBUSY (open).
+ * sr_stats_update: the batches of one route launch (count in 1..SR_MAX_BATCHES_PER_LAUNCH), asynchronous on the
+ *   context's stream; it allocates nothing, so it can be captured in a graph. d_hashes as the route launch
+ *   wrote them (sr_batch.d_hashes). -EINVAL before any launch for a null required pointer (d_n_records; d_recs
+ *   and d_hashes with max_records > 0; d_bytes with nbytes > 0), d_hashes == NULL, a bad count or a context
+ *   that is not open; nbytes and max_records at most 0xFFFFFFF0.
+ * sr_stats_reset : back to the state after open, asynchronous.
+ * sr_stats_read  : synchronises the stream and returns a host snapshot (sr_stats_free). Hot entries carry
+ *   lines = est(hash) from this snapshot and are sorted by lines descending, then hash ascending.
+ * sr_stats_close : waits for the stream and frees the stage, switch included (sr_close does it too); the stage
+ *   can then be opened again with another configuration. 0, -EINVAL, -EBUSY (a slot is in flight).
+ *
+ * Host only (no GPU; on any snapshot, also one a caller assembled itself: the arrays have the sizes noted in
+ * the structure, `hot` has room for cfg.hot_slots entries):
+ *   sr_name_hash        : the reference's sdbm over `len` bytes with signed `char` (sr-main.c:120-134);
+ *   sr_stats_estimate   : est(hash);
+ *   sr_stats_cardinality: the distinct names of `shard`, or of all shards together (SR_STATS_ALL: register-wise
+ *     maximum). The standard estimator: alpha_m * m^2 / sum(2^-reg), m = 2^p; linear counting m * ln(m / V)
+ *     when that is at most 2.5 m and V > 0 registers are zero; alpha = 0.673 / 0.697 / 0.709 for m = 16 / 32 /
+ *     64, else 0.7213 / (1 + 1.079 / m); no large-range correction. A negative value: bad arguments;
+ *   sr_stats_merge      : `from` added into `into` (same config and n_downstreams, else -EINVAL): counters and
+ *     cells add, registers take the maximum, the hot entries are united, estimated again and sorted again;
+ *     hot_overflow is set when either had it or the union does not fit. This is what lets several data
+ *     threads or GPUs give one answer. */
+#define SR_STATS_NAME_MAX   108u      /* name bytes kept per hot entry: an entry is 128 bytes */
+#define SR_STATS_ALL        0xFFFFFFFFu
+#define SR_STATS_MIN_P      4u
+#define SR_STATS_MAX_P      12u
+#define SR_STATS_MAX_REGS   67108864u /* 2^26 registers over all shards */
+#define SR_STATS_MAX_ROWS   8u
+#define SR_STATS_MIN_WIDTH  256u
+#define SR_STATS_MAX_CELLS  16384u
+#define SR_STATS_MIN_SLOTS  4u
+#define SR_STATS_MAX_SLOTS  4096u
+#define SR_STATS_DEFAULT_P          10u
+#define SR_STATS_DEFAULT_ROWS       4u
+#define SR_STATS_DEFAULT_WIDTH      4096u
+#define SR_STATS_DEFAULT_SLOTS      256u
+#define SR_STATS_DEFAULT_HOT_DIV    256u
+#define SR_STATS_DEFAULT_HOT_MIN    1024u
+
+typedef struct sr_stats_config {
+    uint32_t hll_p, cms_rows, cms_width, hot_slots, hot_div, hot_min_lines;
+} sr_stats_config;
+
+typedef struct sr_stats_batch {
+    const uint8_t *d_bytes; size_t nbytes;        /* the routed batch                                     */
+    const sr_record *d_recs;                      /* input-order records (sr_batch.d_out)                 */
+    const uint64_t *d_n_records; size_t max_records;
+    const uint64_t *d_hashes;                     /* max_records u64 (sr_batch.d_hashes); required        */
+} sr_stats_batch;
+
+typedef struct sr_stats_hot {
+    uint64_t hash;
+    uint64_t lines;                               /* est(hash) in the snapshot that holds the entry       */
+    uint32_t name_len;                            /* the name's full length                               */
+    uint8_t name[SR_STATS_NAME_MAX];              /* its first bytes, zero filled                         */
+} sr_stats_hot;
+
+typedef struct sr_stats_snapshot {
+    sr_stats_config cfg;                          /* the effective values (defaults filled in)            */
+    uint32_t n_downstreams;
+    uint32_t hot_overflow;
+    uint64_t lines[4], bytes[4];                  /* per sr_verdict                                       */
+    uint64_t ignored;
+    uint64_t *shard_lines, *shard_bytes;          /* [n_downstreams]                                      */
+    uint8_t *regs;                                /* [n_downstreams << hll_p], shard major                */
+    uint64_t *cells;                              /* [cms_rows * cms_width], row major                    */
+    sr_stats_hot *hot;                            /* n_hot entries, room for cfg.hot_slots                */
+    uint32_t n_hot;
+} sr_stats_snapshot;
+
+int sr_stats_open(sr_ctx *ctx, const sr_stats_config *cfg);
+int sr_stats_update(sr_ctx *ctx, const sr_stats_batch *batches, size_t count);
+int sr_stats_reset(sr_ctx *ctx);
+int sr_stats_read(sr_ctx *ctx, sr_stats_snapshot **out);
+void sr_stats_free(sr_stats_snapshot *snap);
+int sr_stats_close(sr_ctx *ctx);
+uint64_t sr_name_hash(const uint8_t *bytes, size_t len);
+uint64_t sr_stats_estimate(const sr_stats_snapshot *snap, uint64_t hash);
+double sr_stats_cardinality(const sr_stats_snapshot *snap, uint32_t shard);
+int sr_stats_merge(sr_stats_snapshot *into, const sr_stats_snapshot *from);
+
+/* The name statistics of the host-memory path. With sr_set_name_stats(ctx, cfg) (cfg as sr_stats_open takes it;
+ * the stage is opened when it is not yet, and an open stage keeps its configuration and state) every later
+ * sr_route_pack_submit / sr_route_pack_submit_slots / sr_route_pack_batch also runs sr_stats_update over the
+ * slot's input-order records and the route kernel's hashes, on the device: the hashes are requested as
+ * sr_set_trace requests them, but nothing more crosses PCIe per batch. Read with sr_stats_read. NULL turns the
+ * switch off (the state stays until sr_stats_close). Off by default: nothing is allocated, launched or copied.
+ * Returns 0, -EINVAL, -ENOMEM, -EBUSY (a slot is in flight). */
+int sr_set_name_stats(sr_ctx *ctx, const sr_stats_config *cfg_or_null);
+
 /* ---- owner side of the multi-GPU regroup: received lines into packets ------------------------------ */
 /* After sr_regroup_launch / sr_regroup_run the lines of the shards a GPU owns lie in d_recv_bytes /
  * d_recv_recs: every source's chunk in source order 0, 1, ..., each chunk batch 0's lines, then batch

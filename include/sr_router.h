@@ -156,6 +156,21 @@ int sr_core_set_device_log(sr_core *core, int on, size_t text_cap, sr_core_log_p
                            sr_core_log_block_fn block);
 int sr_core_device_log_stats(const sr_core *core, uint64_t *device_batches, uint64_t *host_batches);
 
+/* Name statistics. With sr_core_set_name_stats(core, cfg) (cfg as sr_stats_open takes it, sr_route.h: all zero
+ * selects the defaults) every later batch of sr_core_route*, sr_core_submit* and sr_core_submit_slots is also
+ * counted on the GPU (sr_set_name_stats): lines and bytes per verdict and shard, distinct names per shard, and
+ * the names that carry the most lines. Nothing more crosses PCIe per batch, and packets, counters, log lines
+ * and their order are the same with the switch on. NULL turns the switch off; the statistics stay readable.
+ * sr_core_name_stats drains first, then returns the snapshot (sr_stats_read; free it with sr_stats_free) and,
+ * with reset != 0, starts the statistics again from zero (sr_stats_reset).
+ * What is counted: the lines of data batches. Ping lines are not (sr_core_ping routes them outside the submit
+ * path). A batch that is taken back after a failed one and routed again is counted twice: the statistics see
+ * every route launch, not every completed batch.
+ * Return 0, -EINVAL (also: sr_core_name_stats before the switch was ever on), -EBUSY (set: a batch is in
+ * flight, drain first), -ENOMEM, -EIO. */
+int sr_core_set_name_stats(sr_core *core, const sr_stats_config *cfg_or_null);
+int sr_core_name_stats(sr_core *core, sr_stats_snapshot **out, int reset);
+
 /* Test hook (fault injection; nothing calls it in the executable): the fail_submit-th call of
  * sr_core_submit* fails as a failed sr_route_pack_submit (the batch is not taken), and the
  * fail_finish-th batch to complete fails as a failed sr_route_pack_result (its packets and log lines

@@ -59,6 +59,8 @@ ABI_FUNCTIONS = (
     "sr_comm_group_open", "sr_comm_group_close", "sr_comm_open_local", "sr_comm_set_timeout", "sr_comm_transport",
     "sr_frame_slots_size", "sr_frame_slots", "sr_route_pack_submit_slots",
     "sr_format_log", "sr_set_logtext", "sr_route_pack_set_prefix", "sr_route_pack_set_ends", "sr_route_pack_logtext",
+    "sr_stats_open", "sr_stats_update", "sr_stats_reset", "sr_stats_read", "sr_stats_free", "sr_stats_close",
+    "sr_name_hash", "sr_stats_estimate", "sr_stats_cardinality", "sr_stats_merge", "sr_set_name_stats",
 )
 SR_LOG_MAX_PREFIX = 256
 SR_LOG_TRACE, SR_LOG_WARN = 0, 3   # sr_log_batch.min_level and the d_levels values
@@ -156,6 +158,122 @@ class SrLogBatch(ctypes.Structure):
                 ("d_text", ctypes.c_void_p), ("text_cap", ctypes.c_size_t), ("d_offsets", ctypes.c_void_p),
                 ("d_levels", ctypes.c_void_p), ("max_msgs", ctypes.c_size_t), ("d_total", ctypes.c_void_p),
                 ("d_n_msgs", ctypes.c_void_p)]
+
+
+class SrStatsConfig(ctypes.Structure):
+    """struct sr_stats_config (include/sr_route.h); all zero selects the defaults."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("hll_p", "cms_rows", "cms_width", "hot_slots", "hot_div",
+                                               "hot_min_lines")]
+
+
+class SrStatsBatch(ctypes.Structure):
+    """struct sr_stats_batch (include/sr_route.h): one routed batch of sr_stats_update."""
+    _fields_ = [("d_bytes", ctypes.c_void_p), ("nbytes", ctypes.c_size_t), ("d_recs", ctypes.c_void_p),
+                ("d_n_records", ctypes.c_void_p), ("max_records", ctypes.c_size_t), ("d_hashes", ctypes.c_void_p)]
+
+
+class SrStatsHot(ctypes.Structure):
+    """struct sr_stats_hot (include/sr_route.h): one hot name, 128 bytes."""
+    _fields_ = [("hash", ctypes.c_uint64), ("lines", ctypes.c_uint64), ("name_len", ctypes.c_uint32),
+                ("name", ctypes.c_uint8 * 108)]
+
+
+SR_STATS_NAME_MAX = 108
+SR_STATS_ALL = 0xFFFFFFFF
+SR_STATS_MAX_CELLS = 16384
+SR_STATS_DEFAULTS = dict(hll_p=10, cms_rows=4, cms_width=4096, hot_slots=256, hot_div=256, hot_min_lines=1024)
+STATS_TILE = 1024   # kStatsTile (csrc/stats_kernel.hpp): records per tile of the statistics kernels
+STATS_LDS_SHARDS = 512   # kStatsLdsShards: per-shard sums in LDS up to this many downstreams
+STATS_HOT_DTYPE = np.dtype([("hash", "<u8"), ("lines", "<u8"), ("name_len", "<u4"), ("name", "u1", (108,))])
+assert STATS_HOT_DTYPE.itemsize == 128 == ctypes.sizeof(SrStatsHot)
+
+
+class SrStatsSnapshot(ctypes.Structure):
+    """struct sr_stats_snapshot (include/sr_route.h)."""
+    _fields_ = [("cfg", SrStatsConfig), ("n_downstreams", ctypes.c_uint32), ("hot_overflow", ctypes.c_uint32),
+                ("lines", ctypes.c_uint64 * 4), ("bytes", ctypes.c_uint64 * 4), ("ignored", ctypes.c_uint64),
+                ("shard_lines", ctypes.c_void_p), ("shard_bytes", ctypes.c_void_p), ("regs", ctypes.c_void_p),
+                ("cells", ctypes.c_void_p), ("hot", ctypes.c_void_p), ("n_hot", ctypes.c_uint32)]
+
+
+class StatsSnapshot:
+    """A sr_stats_snapshot in numpy arrays this object owns; `.c` is the C structure over them, for the host-only
+    entry points (sr_stats_estimate, sr_stats_cardinality, sr_stats_merge). Fields: cfg (dict), n, lines[4],
+    bytes[4], ignored, shard_lines[n], shard_bytes[n], regs[n, 2^p] u8, cells[rows, width] u64, hot_overflow,
+    hot (STATS_HOT_DTYPE, room for hot_slots; the first n_hot are valid)."""
+
+    def __init__(self, cfg: dict, n: int):
+        self.cfg, self.n = dict(cfg), int(n)
+        self.lines = np.zeros(4, np.uint64)
+        self.bytes = np.zeros(4, np.uint64)
+        self.ignored = 0
+        self.hot_overflow = 0
+        self.shard_lines = np.zeros(max(n, 1), np.uint64)[:n]
+        self.shard_bytes = np.zeros(max(n, 1), np.uint64)[:n]
+        self.regs = np.zeros((n, 1 << cfg["hll_p"]), np.uint8)
+        self.cells = np.zeros((cfg["cms_rows"], cfg["cms_width"]), np.uint64)
+        self._hot = np.zeros(cfg["hot_slots"], STATS_HOT_DTYPE)
+        self.n_hot = 0
+        self.c = SrStatsSnapshot()
+
+    @property
+    def hot(self) -> np.ndarray:
+        return self._hot[: self.n_hot]
+
+    def set_hot(self, entries: np.ndarray) -> None:
+        self.n_hot = len(entries)
+        self._hot[: self.n_hot] = entries
+
+    def sync_c(self) -> "SrStatsSnapshot":
+        """The C structure pointing at this object's arrays, scalars copied in."""
+        c = self.c
+        c.cfg = SrStatsConfig(**self.cfg)
+        c.n_downstreams, c.hot_overflow, c.ignored, c.n_hot = self.n, int(self.hot_overflow), int(self.ignored), self.n_hot
+        for v in range(4):
+            c.lines[v], c.bytes[v] = int(self.lines[v]), int(self.bytes[v])
+        c.shard_lines, c.shard_bytes = self.shard_lines.ctypes.data, self.shard_bytes.ctypes.data
+        c.regs, c.cells, c.hot = self.regs.ctypes.data, self.cells.ctypes.data, self._hot.ctypes.data
+        return c
+
+    def from_c(self) -> None:
+        """The scalars back from the C structure (after sr_stats_merge wrote through it)."""
+        c = self.c
+        self.hot_overflow, self.ignored, self.n_hot = int(c.hot_overflow), int(c.ignored), int(c.n_hot)
+        self.lines[:] = list(c.lines)
+        self.bytes[:] = list(c.bytes)
+
+    @classmethod
+    def copy_of(cls, c: "SrStatsSnapshot") -> "StatsSnapshot":
+        cfg = {k: int(getattr(c.cfg, k)) for k, _ in SrStatsConfig._fields_}
+        s = cls(cfg, int(c.n_downstreams))
+        take = lambda addr, count, dt: (np.frombuffer(ctypes.string_at(addr, count * np.dtype(dt).itemsize), dtype=dt).copy()
+                                        if count else np.zeros(0, dt))
+        s.lines[:], s.bytes[:] = list(c.lines), list(c.bytes)
+        s.ignored, s.hot_overflow = int(c.ignored), int(c.hot_overflow)
+        s.shard_lines = take(c.shard_lines, s.n, np.uint64)
+        s.shard_bytes = take(c.shard_bytes, s.n, np.uint64)
+        s.regs = take(c.regs, s.n << cfg["hll_p"], np.uint8).reshape(s.n, 1 << cfg["hll_p"])
+        s.cells = take(c.cells, cfg["cms_rows"] * cfg["cms_width"], np.uint64).reshape(cfg["cms_rows"], cfg["cms_width"])
+        s.set_hot(take(c.hot, int(c.n_hot), STATS_HOT_DTYPE))
+        return s
+
+
+def name_hash(name: bytes) -> int:
+    """sr_name_hash: the reference's sdbm (signed char) over the bytes of a name."""
+    return int(lib().sr_name_hash(name, len(name)))
+
+
+def stats_estimate(snap: StatsSnapshot, h: int) -> int:
+    return int(lib().sr_stats_estimate(ctypes.byref(snap.sync_c()), h))
+
+
+def stats_cardinality(snap: StatsSnapshot, shard: int = SR_STATS_ALL) -> float:
+    return float(lib().sr_stats_cardinality(ctypes.byref(snap.sync_c()), shard))
+
+
+def stats_merge(into: StatsSnapshot, other: StatsSnapshot) -> None:
+    _check(lib().sr_stats_merge(ctypes.byref(into.sync_c()), ctypes.byref(other.sync_c())), "sr_stats_merge")
+    into.from_c()
 
 
 class SrOwnerBatch(ctypes.Structure):
@@ -311,6 +429,17 @@ def _load_route_lib() -> ctypes.CDLL:
         "sr_route_pack_set_ends": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_size_t]),
         "sr_route_pack_logtext": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(vp), u64p, ctypes.POINTER(vp),
                                                  ctypes.POINTER(vp), c_size_p]),
+        "sr_stats_open": (ctypes.c_int, [vp, ctypes.POINTER(SrStatsConfig)]),
+        "sr_stats_update": (ctypes.c_int, [vp, ctypes.POINTER(SrStatsBatch), ctypes.c_size_t]),
+        "sr_stats_reset": (ctypes.c_int, [vp]),
+        "sr_stats_read": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.POINTER(SrStatsSnapshot))]),
+        "sr_stats_free": (None, [ctypes.POINTER(SrStatsSnapshot)]),
+        "sr_stats_close": (ctypes.c_int, [vp]),
+        "sr_name_hash": (ctypes.c_uint64, [ctypes.c_char_p, ctypes.c_size_t]),
+        "sr_stats_estimate": (ctypes.c_uint64, [ctypes.POINTER(SrStatsSnapshot), ctypes.c_uint64]),
+        "sr_stats_cardinality": (ctypes.c_double, [ctypes.POINTER(SrStatsSnapshot), ctypes.c_uint32]),
+        "sr_stats_merge": (ctypes.c_int, [ctypes.POINTER(SrStatsSnapshot), ctypes.POINTER(SrStatsSnapshot)]),
+        "sr_set_name_stats": (ctypes.c_int, [vp, ctypes.POINTER(SrStatsConfig)]),
     }
     for name in ABI_FUNCTIONS:
         if os.environ.get("SR_ROUTE_LIB") and not hasattr(lib, name):
@@ -696,6 +825,45 @@ class Router:
             batch = SrLogBatch(**{k: (v or None) if k.startswith("d_") else v for k, v in fields.items()})
             batch.prefix_len[0], batch.prefix_len[1] = int(plen[0]), int(plen[1])
         _check(self._lib.sr_format_log(self._h, ctypes.byref(batch)), "sr_format_log")
+
+    def stats_open(self, **cfg) -> None:
+        """sr_stats_open: the name statistics of this context (fields of sr_stats_config; none = the defaults)."""
+        _check(self._lib.sr_stats_open(self._h, ctypes.byref(SrStatsConfig(**cfg))), "sr_stats_open")
+
+    @staticmethod
+    def stats_batches(batches):
+        """The sr_stats_batch array of [(d_bytes, nbytes, d_recs, d_n_records, max_records, d_hashes), ...] (raw
+        device pointers, 0 = NULL; reusable)."""
+        arr = (SrStatsBatch * max(len(batches), 1))()
+        for i, (db, nb, dr, dn, mr, dh) in enumerate(batches):
+            arr[i] = SrStatsBatch(db or None, nb, dr or None, dn or None, mr, dh or None)
+        return arr
+
+    def stats_update(self, batches) -> None:
+        """sr_stats_update over the batches of one route launch (as stats_batches takes them, or its array),
+        asynchronous on the context's stream."""
+        arr = batches if isinstance(batches, ctypes.Array) else self.stats_batches(batches)
+        _check(self._lib.sr_stats_update(self._h, arr, len(batches)), "sr_stats_update")
+
+    def stats_reset(self) -> None:
+        _check(self._lib.sr_stats_reset(self._h), "sr_stats_reset")
+
+    def stats_close(self) -> None:
+        _check(self._lib.sr_stats_close(self._h), "sr_stats_close")
+
+    def stats_read(self) -> StatsSnapshot:
+        """sr_stats_read: waits for the stream and returns a copy of the snapshot."""
+        p = ctypes.POINTER(SrStatsSnapshot)()
+        _check(self._lib.sr_stats_read(self._h, ctypes.byref(p)), "sr_stats_read")
+        try:
+            return StatsSnapshot.copy_of(p.contents)
+        finally:
+            self._lib.sr_stats_free(p)
+
+    def set_name_stats(self, on: bool = True, **cfg) -> None:
+        """sr_set_name_stats: later route_pack submissions also update the name statistics on the device."""
+        _check(self._lib.sr_set_name_stats(self._h, ctypes.byref(SrStatsConfig(**cfg)) if on else None),
+               "sr_set_name_stats")
 
     def route_pack_submit_slots(self, slot: int, slots, stride: int, lens, fill=None) -> None:
         """sr_route_pack_submit_slots (asynchronous): `slots` is page-locked memory (a HostBuffer, or its

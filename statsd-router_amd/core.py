@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from . import LIB_DIR, SrError, _check, alive_words, lib
+from . import LIB_DIR, SrError, SrStatsConfig, SrStatsSnapshot, StatsSnapshot, _check, alive_words, lib
 
 ROUTER_LIB = os.path.join(LIB_DIR, "libsr_router.so")
 SR_TRACE, SR_DEBUG, SR_INFO, SR_WARN, SR_ERROR = range(5)
@@ -76,6 +76,10 @@ def router_lib() -> ctypes.CDLL:
         L.sr_core_submit_slots.argtypes = [vp, ctypes.c_int, vp, ctypes.c_size_t]
         L.sr_core_set_device_log.restype = ctypes.c_int
         L.sr_core_set_device_log.argtypes = [vp, ctypes.c_int, ctypes.c_size_t, LOG_PREFIX_FN, LOG_BLOCK_FN]
+        L.sr_core_set_name_stats.restype = ctypes.c_int
+        L.sr_core_set_name_stats.argtypes = [vp, ctypes.POINTER(SrStatsConfig)]
+        L.sr_core_name_stats.restype = ctypes.c_int
+        L.sr_core_name_stats.argtypes = [vp, ctypes.POINTER(ctypes.POINTER(SrStatsSnapshot)), ctypes.c_int]
         L.sr_core_device_log_stats.restype = ctypes.c_int
         L.sr_core_device_log_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         _RLIB = L
@@ -226,6 +230,21 @@ class Core:
         d, h = ctypes.c_uint64(), ctypes.c_uint64()
         _check(self._L.sr_core_device_log_stats(self._h, ctypes.byref(d), ctypes.byref(h)), "sr_core_device_log_stats")
         return d.value, h.value
+
+    def set_name_stats(self, on: bool = True, **cfg) -> None:
+        """sr_core_set_name_stats: later batches are also counted on the GPU (fields of sr_stats_config; none =
+        the defaults)."""
+        _check(self._L.sr_core_set_name_stats(self._h, ctypes.byref(SrStatsConfig(**cfg)) if on else None),
+               "sr_core_set_name_stats")
+
+    def name_stats(self, reset: bool = False) -> StatsSnapshot:
+        """sr_core_name_stats: drains, then a copy of the snapshot; reset starts the statistics again."""
+        p = ctypes.POINTER(SrStatsSnapshot)()
+        _check(self._L.sr_core_name_stats(self._h, ctypes.byref(p), 1 if reset else 0), "sr_core_name_stats")
+        try:
+            return StatsSnapshot.copy_of(p.contents)
+        finally:
+            lib().sr_stats_free(p)
 
     def set_layout(self, layout: int) -> None:
         """sr_set_layout on the core's device context (sr_core_context)."""

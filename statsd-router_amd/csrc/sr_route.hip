@@ -26,6 +26,7 @@
 #include "payload_kernel.hpp"
 #include "regroup_kernel.hpp"
 #include "route_host.hpp"
+#include "stats_kernel.hpp"
 
 using namespace srk;
 
@@ -79,6 +80,8 @@ struct sr_ctx {
     size_t log_cap, log_msgs;     // the slots' text bytes and index entries
     uint32_t log_max_msg;
     uint32_t *d_ends;             // slot submissions at TRACE: the frame kernels' datagram ends (SR_MAX_SLOTS)
+    StatsState stats;             // sr_stats_open: the name statistics' device state
+    int name_stats;               // sr_set_name_stats: submissions also run sr_stats_update on the device
     // packing knobs (sr_set_knob): forced chunk lines (0: by shape), XCD-local chunks, chain walked in emit
     uint32_t mtu_chunk;
     int mtu_xcd, mtu_walk;
@@ -233,6 +236,7 @@ void sr_close(sr_ctx *c) {
     free_ptr(c->d_frame);
     free_ptr(c->d_log);
     free_ptr(c->d_ends);
+    free_ptr(c->stats.d_base);
     for (auto &sl : c->slot) {
         if (sl.host) (void)hipHostFree(sl.host);
         if (sl.thost) (void)hipHostFree(sl.thost);
@@ -979,6 +983,198 @@ static int log_impl(sr_ctx *c, const sr_log_batch *b) {
 
 int sr_format_log(sr_ctx *c, const sr_log_batch *b) { return log_impl(c, b); }
 
+// ---- name statistics (stats_kernel.hpp, stats_host.hpp) ---------------------------------------------
+// One device allocation holds the whole state, so a reset is one memset and a read one copy:
+// counters | per-shard lines, bytes | cells | hot keys A, B | hot names | registers (u32 each)
+static int stats_open_impl(sr_ctx *c, const sr_stats_config *cfg) {
+    if (!c) return -EINVAL;
+    StatsState &st = c->stats;
+    if (st.open) return -EBUSY;
+    sr_stats_config r;
+    if (stats_resolve(cfg, c->ds.nds, &r) != 0) return -EINVAL;
+    const size_t nds = c->ds.nds, cells = (size_t)r.cms_rows * r.cms_width;
+    st.o_shard = kStatsCtrs * sizeof(uint64_t);
+    st.o_cells = st.o_shard + 2 * nds * sizeof(uint64_t);
+    st.o_ka = st.o_cells + cells * sizeof(uint64_t);
+    st.o_kb = st.o_ka + (size_t)r.hot_slots * sizeof(uint64_t);
+    st.o_names = st.o_kb + (size_t)r.hot_slots * sizeof(uint64_t);
+    st.o_regs = st.o_names + (size_t)r.hot_slots * sizeof(StatsHotName);
+    st.bytes = st.o_regs + (nds << r.hll_p) * sizeof(uint32_t);
+    (void)hipSetDevice(c->device);
+    if (hipMalloc(&st.d_base, st.bytes) != hipSuccess) {
+        st.d_base = nullptr;
+        (void)hipGetLastError();
+        return -ENOMEM;
+    }
+    if (hipMemsetAsync(st.d_base, 0, st.bytes, c->stream) != hipSuccess) {
+        free_ptr(st.d_base);
+        st.d_base = nullptr;
+        return -EIO;
+    }
+    // the sketch in LDS next to the per-shard sums can pass the 64 KiB default (set here, not in a capture)
+    ensure_dyn_lds((const void *)stats_count_kernel<true>, SR_STATS_MAX_CELLS * 4);
+    ensure_dyn_lds((const void *)stats_count_kernel<false>, SR_STATS_MAX_CELLS * 4);
+    st.cfg = r;
+    st.open = 1;
+    return 0;
+}
+
+static int stats_update_impl(sr_ctx *c, const sr_stats_batch *batches, size_t count) {
+    static_assert(kStatsMaxBatches == (int)SR_MAX_BATCHES_PER_LAUNCH, "launch batch limit");
+    if (!c || !c->stats.open || !batches || count == 0 || count > (size_t)kStatsMaxBatches) return -EINVAL;
+    const StatsState &st = c->stats;
+    StatsArgs a;
+    memset(&a, 0, sizeof(a));
+    uint64_t tiles = 0;   // the grid's bound only (the kernels number the tiles by the device's counts)
+    for (size_t j = 0; j < count; ++j) {
+        const sr_stats_batch &b = batches[j];
+        if (!b.d_n_records || !b.d_hashes || (b.max_records && !b.d_recs) || (b.nbytes && !b.d_bytes)) return -EINVAL;
+        if (b.nbytes > 0xFFFFFFF0ull || b.max_records > 0xFFFFFFF0ull) return -EINVAL;
+        StatsBatchArg &o = a.b[j];
+        o.bytes = b.d_bytes;
+        o.recs = b.d_recs;
+        o.n_records = b.d_n_records;
+        o.hashes = b.d_hashes;
+        o.nbytes = (uint32_t)b.nbytes;
+        o.max_records = (uint32_t)b.max_records;
+        // the host-memory path gives max_records = nbytes (a line has at least a byte): the grid goes by the
+        // lines a batch of this size plausibly holds, the kernels by the device's counts
+        const uint64_t likely = (uint64_t)b.nbytes / kStatsGridLineBytes + 1u;
+        const uint64_t room = b.max_records < likely ? b.max_records : likely;
+        tiles += (room + kStatsTile - 1) / kStatsTile;
+    }
+    if (!tiles) return 0;
+    uint8_t *const base = st.d_base;
+    a.ctr = (unsigned long long *)base;
+    a.shard = (unsigned long long *)(base + st.o_shard);
+    a.cells = (unsigned long long *)(base + st.o_cells);
+    a.key_a = (unsigned long long *)(base + st.o_ka);
+    a.key_b = (unsigned long long *)(base + st.o_kb);
+    a.names = (StatsHotName *)(base + st.o_names);
+    a.regs = (uint32_t *)(base + st.o_regs);
+    a.nb = (uint32_t)count;
+    a.nds = c->ds.nds;
+    a.p = st.cfg.hll_p;
+    a.rows = st.cfg.cms_rows;
+    a.width = st.cfg.cms_width;
+    a.slots = st.cfg.hot_slots;
+    a.hot_div = st.cfg.hot_div;
+    a.hot_min = st.cfg.hot_min_lines;
+    (void)hipSetDevice(c->device);
+    // the grid by the records: a few thousand lines get a few workgroups, never more than kStatsGroups
+    const uint64_t want = (tiles + kStatsTilesPerGroup - 1) / kStatsTilesPerGroup;
+    const dim3 grid((uint32_t)(want < (uint64_t)kStatsGroups ? want : (uint64_t)kStatsGroups));
+    const size_t lds = (size_t)a.rows * a.width * sizeof(uint32_t);
+    if (a.nds <= (uint32_t)kStatsLdsShards)
+        hipLaunchKernelGGL(stats_count_kernel<true>, grid, dim3(kStatsBlock), lds, c->stream, a);
+    else
+        hipLaunchKernelGGL(stats_count_kernel<false>, grid, dim3(kStatsBlock), lds, c->stream, a);
+    hipLaunchKernelGGL(stats_hot_kernel, grid, dim3(kStatsBlock), 0, c->stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+int sr_stats_open(sr_ctx *c, const sr_stats_config *cfg) { return stats_open_impl(c, cfg); }
+
+int sr_stats_update(sr_ctx *c, const sr_stats_batch *batches, size_t count) {
+    return stats_update_impl(c, batches, count);
+}
+
+int sr_stats_reset(sr_ctx *c) {
+    if (!c || !c->stats.open) return -EINVAL;
+    (void)hipSetDevice(c->device);
+    return hipMemsetAsync(c->stats.d_base, 0, c->stats.bytes, c->stream) == hipSuccess ? 0 : -EIO;
+}
+
+int sr_stats_close(sr_ctx *c) {
+    if (!c) return -EINVAL;
+    for (int k = 0; k < 3; ++k)
+        if (c->slot[k].busy) return -EBUSY;
+    if (!c->stats.open) return 0;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    free_ptr(c->stats.d_base);
+    memset(&c->stats, 0, sizeof(c->stats));
+    c->name_stats = 0;
+    return 0;
+}
+
+int sr_stats_read(sr_ctx *c, sr_stats_snapshot **out) {
+    if (out) *out = nullptr;
+    if (!c || !out || !c->stats.open) return -EINVAL;
+    const StatsState &st = c->stats;
+    const uint32_t nds = c->ds.nds;
+    (void)hipSetDevice(c->device);
+    uint8_t *h = (uint8_t *)malloc(st.bytes);
+    sr_stats_snapshot *s = stats_snap_alloc(st.cfg, nds);
+    if (!h || !s) {
+        free(h);
+        free(s);
+        return -ENOMEM;
+    }
+    if (hipMemcpyAsync(h, st.d_base, st.bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) {
+        free(h);
+        free(s);
+        return -EIO;
+    }
+    const uint64_t *ctr = (const uint64_t *)h;
+    for (int v = 0; v < 4; ++v) {
+        s->lines[v] = ctr[kStatsCtrLines + v];
+        s->bytes[v] = ctr[kStatsCtrBytes + v];
+    }
+    s->ignored = ctr[kStatsCtrIgnored];
+    s->hot_overflow = ctr[kStatsCtrOverflow] ? 1u : 0u;
+    memcpy(s->shard_lines, h + st.o_shard, (size_t)nds * sizeof(uint64_t));
+    memcpy(s->shard_bytes, h + st.o_shard + (size_t)nds * sizeof(uint64_t), (size_t)nds * sizeof(uint64_t));
+    memcpy(s->cells, h + st.o_cells, (size_t)st.cfg.cms_rows * st.cfg.cms_width * sizeof(uint64_t));
+    const uint32_t *regs = (const uint32_t *)(h + st.o_regs);
+    for (size_t i = 0, n = (size_t)nds << st.cfg.hll_p; i < n; ++i) s->regs[i] = (uint8_t)regs[i];
+    const uint64_t *ka = (const uint64_t *)(h + st.o_ka), *kb = (const uint64_t *)(h + st.o_kb);
+    const StatsHotName *names = (const StatsHotName *)(h + st.o_names);
+    for (uint32_t k = 0; k < st.cfg.hot_slots; ++k) {
+        if (!kb[k]) continue;   // B is set last: a slot without it holds nothing
+        sr_stats_hot &e = s->hot[s->n_hot++];
+        e.hash = (ka[k] >> 32) << 32 | kb[k] >> 32;
+        e.name_len = names[k].name_len;
+        memcpy(e.name, names[k].name, SR_STATS_NAME_MAX);
+    }
+    stats_sort_hot(s);
+    free(h);
+    *out = s;
+    return 0;
+}
+
+void sr_stats_free(sr_stats_snapshot *snap) { free(snap); }
+
+uint64_t sr_name_hash(const uint8_t *bytes, size_t len) { return (bytes || !len) ? stats_name_hash(bytes, len) : 0; }
+
+uint64_t sr_stats_estimate(const sr_stats_snapshot *snap, uint64_t hash) {
+    return stats_snap_ok(snap) ? stats_estimate(snap, hash) : 0;
+}
+
+double sr_stats_cardinality(const sr_stats_snapshot *snap, uint32_t shard) {
+    if (!stats_snap_ok(snap) || (shard != SR_STATS_ALL && shard >= snap->n_downstreams)) return -1.0;
+    return stats_cardinality(snap, shard);
+}
+
+int sr_stats_merge(sr_stats_snapshot *into, const sr_stats_snapshot *from) { return stats_merge(into, from); }
+
+int sr_set_name_stats(sr_ctx *c, const sr_stats_config *cfg) {
+    if (!c) return -EINVAL;
+    for (int k = 0; k < 3; ++k)
+        if (c->slot[k].busy) return -EBUSY;
+    if (!cfg) {
+        c->name_stats = 0;
+        return 0;
+    }
+    if (!c->stats.open) {
+        const int rc = stats_open_impl(c, cfg);
+        if (rc) return rc;
+    }
+    c->name_stats = 1;
+    return 0;
+}
+
 static int grow(void **ptr, size_t *cap, size_t need, size_t elem) {
     if (need <= *cap) return 0;
     free_ptr(*ptr);
@@ -1183,9 +1379,9 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
         // over 1024 shards with some dead the route kernel also writes the hashes: the probed-dead
         // replay then reads 8 bytes per line instead of re-hashing the names (probed_dead_kernel);
         // up to 1024 the probes note the dead shards themselves
-        // TRACE (sr_set_trace) needs every line's hash too (sr-main.c:91)
+        // TRACE (sr_set_trace) needs every line's hash too (sr-main.c:91), and so do the name statistics
         uint64_t *hashes = nullptr;
-        if (c->trace || log_trace || c->ds.replay_wants_hashes()) {
+        if (c->trace || log_trace || c->name_stats || c->ds.replay_wants_hashes()) {
             if ((rc = grow((void **)&c->d_hash, &c->d_hash_cap, full, sizeof(uint64_t)))) return rc;
             hashes = c->d_hash;
         }
@@ -1252,6 +1448,10 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
         sl.logged = 1;
         sl.stage_plen[0] = sl.stage_plen[1] = 0;   // staged for one submission
         sl.stage_ends = 0;
+    }
+    if (c->name_stats && nbytes) {   // the input-order records and the hashes never leave the device
+        const sr_stats_batch sb{c->d_in, nbytes, c->d_out, c->d_count, cap, c->d_hash};
+        if ((rc = stats_update_impl(c, &sb, 1))) return rc;
     }
     if (hipEventRecord(sl.done, c->stream) != hipSuccess) return -EIO;
     sl.busy = 1;
