@@ -21,7 +21,8 @@
 //     the kOcc8 variant) into a padded
 //     LDS image (17-dword rows: conflict-free per-thread rows); '\n' and ':' bit masks of the
 //     thread's 64 bytes from the load registers (8 VALU per dword for both patterns); the tile's '\n'
-//     count published at once in a status granule for the scanner.
+//     count published at once in a status granule for the scanner (kOcc8: ahead of the image stores,
+//     the ':' masks and the barrier, by whichever wave has its count last; tile_load).
 //   * Record numbering: the scanner polls its batch's tile counts (two polls in flight, 64 tiles per
 //     poll) and publishes each tile's first record index (bases granule: plain store when the tile
 //     shares the scanner's XCD, sc1 otherwise); a second scanner wave does the stores. A tile reads
@@ -408,6 +409,25 @@ __device__ __forceinline__ uint32_t nl_colon_mask16(uint4 v) {   // '\n' mask | 
     const uint32_t cl = (cn + (ch << 8)) >> 7;
     return nl | (cl << 16);
 }
+// One pattern's half of nl_colon_mask16 (the same flags, so the same mask): 16-bit mask of the bytes of a
+// 16-byte piece equal to the byte replicated in PAT (bit 7 clear), 4 VALU per dword. OPAQUE: the piece's
+// dwords pass through an empty asm first, so that this pass is computed where it stands (not hoisted
+// above what precedes it) and shares no masked-byte registers with an earlier pass over the same piece.
+template <uint32_t PAT, bool OPAQUE = false>
+__device__ __forceinline__ uint32_t byte_mask16(uint4 v) {
+    uint32_t xs[4] = {v.x, v.y, v.z, v.w};
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        uint32_t x = xs[d];
+        if (OPAQUE) asm volatile("" : "+v"(x));
+        const uint32_t f = nor_and(xor_add(x & 0x7F7F7F7Fu, PAT, 0x7F7F7F7Fu), x, 0x80808080u);
+        const uint32_t w = (d & 1) ? 0x80402010u : 0x08040201u;
+        if (d < 2) lo = __builtin_amdgcn_udot4(f, w, lo, false);
+        else hi = __builtin_amdgcn_udot4(f, w, hi, false);
+    }
+    return (lo + (hi << 8)) >> 7;
+}
 
 // number of bytes equal to the replicated pattern
 __device__ __forceinline__ uint32_t eq_count4(uint32_t x, uint32_t pat) {
@@ -774,8 +794,10 @@ __device__ __forceinline__ void mark_tile_end(const RouteParams &p, const uint32
 // a 256-thread workgroup is admitted min(8, floor(800 / (ceil(sgpr / 16) * 16 + 16))) times per CU,
 // which is 7 from 81 SGPRs on, whatever the occupancy query and the compiler's remark say.
 // (ABL_STAMPS, the diagnostic build of tools/stamps_route.hip, keeps the shape of what it stamps.)
+// The ablation builds of tools/ablate_route.hip (ABL_ bits beside KV_ALIVE) keep the shape of the variant
+// they ablate as well: its LDS layout, its occupancy target and its hash engine.
 template <unsigned ABL>
-constexpr bool kOcc8 = (ABL & ~ABL_STAMPS) == (KV_UNIFORM | KV_ALIVE);
+constexpr bool kOcc8 = (ABL & ~kAblBits) == (KV_UNIFORM | KV_ALIVE);
 // kMx: the route_kernel variants that hash names on the matrix cores (sdbm_mx below; -DSR_SDBM_MFMA=0
 // keeps the VALU Horner): that one, and the uniform KV_DEFER1 variant (two or more dead shards), whose
 // probe takes kernel arguments and leaves the pad dwords free for the tables just the same.
@@ -864,6 +886,9 @@ struct SmemT<true> {
     uint32_t hist[kHistKeys];
     uint32_t epoch, base;
     uint32_t scan_head, scan_pub, scan_total;
+    // the tile's count publish (tile_load): (waves arrived << 16) | the sum of their '\n' counts, zeroed
+    // at tile entry; a tile holds at most kTile < 2^16 '\n' bytes
+    uint32_t cnt_word;
     __device__ __forceinline__ void put_pow(int w, uint32_t v) {
         img[w * 17 + 16] = v;
         if (w < 8) ((uint32_t *)&kp_rem[0])[w] = v;
@@ -1098,6 +1123,18 @@ template <int O0, int O1>
 __device__ __forceinline__ void ds_write2_at(uint32_t base, uint32_t a, uint32_t b) {
     asm volatile("ds_write2_b32 %0, %1, %2 offset0:%3 offset1:%4" ::"v"(base), "v"(a), "v"(b), "i"(O0), "i"(O1)
                  : "memory");
+}
+
+// Atomic add to an LDS word (workgroup scope by construction), returning the value before it. The
+// instruction itself: from a single lane the compiler's atomic optimiser wraps __hip_atomic_fetch_add in a
+// scan loop over the active lanes (a dozen scalar instructions for the one lane).
+__device__ __forceinline__ uint32_t lds_add_rtn(uint32_t *word, uint32_t v) {
+    uint32_t before;
+    asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)"
+                 : "=v"(before)
+                 : "v"(lds_addr(word)), "v"(v)
+                 : "memory");
+    return before;
 }
 
 // store / load one 16-byte chunk at image byte b (b % 16 == 0: never crosses a row)
@@ -1459,6 +1496,49 @@ __device__ __forceinline__ void tile_load(const RouteParams &p, S &sm, const Til
     uint64_t *const status = p.status + p.b[in.bi].sbase;
 
     stamp<ABL>(p, tid, g, 0);
+    if constexpr (kOcc8<ABL>) {
+        // The count first: the scanner's chain (count -> base -> this tile's and its successors' first
+        // records) starts at the publish, and of the work on the tile's bytes it needs only the '\n'
+        // count. So: the '\n' flags of the lane's 64 bytes and the wave's add-scan (the line phase's c_in),
+        // then each wave's last lane adds (1 << 16) | its wave's count to sm.cnt_word (zeroed at tile
+        // entry, a barrier ago), and the one that finds three arrivals before it holds the tile's count
+        // and stores the granule: no barrier, and no wave waits for another. The image stores and the
+        // ':' flags follow; the ':' pass masks the bytes again (one VALU per dword) rather than keep the
+        // 16 masked dwords live across the publish.
+        static_assert(kTile < (1 << 16) && kWaves < (1 << 16), "count and arrivals share a word");
+        uint32_t n[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) n[k] = byte_mask16<0x0A0A0A0Au>(in.v[k]);
+        nlm = ((uint64_t)(n[2] | (n[3] << 16)) << 32) | (n[0] | (n[1] << 16));
+        c_in = wave_incl_add32((uint32_t)__popcll(nlm));   // also the line scan's '\n' count
+        if (lane == 63) {
+            sm.wave_cnt[wave] = c_in;
+            const uint32_t before = lds_add_rtn(&sm.cnt_word, c_in + (1u << 16));
+            if ((before >> 16) == (uint32_t)kWaves - 1u) {   // the fourth arrival publishes the tile's count
+                if (ABL & ABL_STAMPS) p.dbg[(size_t)g * 16 + 1] = __builtin_amdgcn_s_memrealtime();
+                const uint32_t tile_count = (before & 0xFFFFu) + c_in;
+                const uint32_t x = xcc_id();
+                const bool same = granule_ok(in.sx, epoch & 0x3FFFFFFFu, kFlagXcc) && (uint32_t)in.sx == x;
+                granule_store(&status[in.t], mk_status(epoch, kFlagAgg, tile_count | ((8u | x) << 28)), same);
+            }
+        }
+        if (tid < kHalo / 16) img_put16(sm, tid * 16, in.hv);
+        const uint32_t rb = lds_addr(&sm.img[(kHalo / 64 + tid) * 17]);
+        ds_write2_at<0, 1>(rb, in.v[0].x, in.v[0].y);
+        ds_write2_at<2, 3>(rb, in.v[0].z, in.v[0].w);
+        ds_write2_at<4, 5>(rb, in.v[1].x, in.v[1].y);
+        ds_write2_at<6, 7>(rb, in.v[1].z, in.v[1].w);
+        ds_write2_at<8, 9>(rb, in.v[2].x, in.v[2].y);
+        ds_write2_at<10, 11>(rb, in.v[2].z, in.v[2].w);
+        ds_write2_at<12, 13>(rb, in.v[3].x, in.v[3].y);
+        ds_write2_at<14, 15>(rb, in.v[3].z, in.v[3].w);
+        uint32_t c[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) c[k] = byte_mask16<0x3A3A3A3Au, true>(in.v[k]);
+        clm = ((uint64_t)(c[2] | (c[3] << 16)) << 32) | (c[0] | (c[1] << 16));
+        wg_barrier();   // the image and sm.wave_cnt[] are complete
+        return;
+    }
     if (tid < kHalo / 16) img_put16(sm, tid * 16, in.hv);
     {
         // 17-dword rows: conflict-free per-lane rows; eight two-dword stores from one base address
@@ -1498,7 +1578,8 @@ __device__ __forceinline__ void tile_load(const RouteParams &p, S &sm, const Til
 template <unsigned ABL, class S>
 __device__ __forceinline__ void tile_lines(const RouteParams &p, S &sm, const TileIn &in, uint32_t epoch,
                                            uint32_t g, uint64_t nlm, uint64_t clm, uint32_t c_in) {
-    stamp<ABL>(p, threadIdx.x, g, 1);
+    // (kOcc8: stamp 1 is the publishing lane's, in tile_load; the barrier behind it is stamp 15)
+    stamp<ABL>(p, threadIdx.x, g, kOcc8<ABL> ? 15 : 1);
     typedef typename S::pos_t pos_t;
     constexpr int kWaves = S::kWaves;
     constexpr int kTileB = S::kTileB;
@@ -1755,7 +1836,7 @@ __device__ __forceinline__ void tile_lines(const RouteParams &p, S &sm, const Ti
                 // (a staged 16-bit position reads 0xFFFF for "no colon": above every line end, as kNone is)
                 const bool fmt_ok = c != kNone && c < e;                                                // :140
                 uint64_t h = 0;
-                if constexpr (kMx<ABL>) {
+                if constexpr (kMx<ABL> && !(ABL & ABL_NO_HASH)) {
                     // the whole wave hashes (matrix instructions): lanes without a name feed zeros
                     const bool mid = !(ABL & ABL_NO_MID_BASE) && !have_base;
                     h = sdbm_mx(sm, act && len_ok && fmt_ok, s + kHalo, c + kHalo, gi, Gl, mid ? base_slot : nullptr,
@@ -2006,6 +2087,12 @@ __attribute__((amdgpu_waves_per_eu((KernelTraits<ABL>::kMinWavesPerSimd), (Kerne
     // is a whole round trip more before the tile can publish its count (+5 % per C2 launch measured)
     in.sx = __hip_atomic_load(&p.ctl->scan_xcc[bi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t ep0 = __hip_atomic_load(&p.ctl->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (kOcc8<ABL>) {
+        // the count word of tile_load's publish starts at zero: set while the tile's loads are in flight,
+        // and a barrier of LDS scope (it waits for no global load) before any wave can add to it
+        if (tid == 0) sm.cnt_word = 0u;
+        wg_barrier();
+    }
     if (kEarlyArrive<ABL> && tid == 0) arrive_count_after(p, blockIdx.x, ep0);
     if constexpr (kMx<ABL>) {
         if (tid < kMxRows) sm.img[tid * 17 + 16] = kp;   // the matrix-core tables (sdbm_mx)

@@ -98,8 +98,9 @@ void run_many(DeviceState &ds, std::vector<uint8_t *> &batches, std::vector<size
         if (f) {
             for (uint32_t t = 0; t < total; ++t) {
                 const uint64_t *d = h.data() + (size_t)t * 16;
-                const uint64_t r[12] = {d[8], d[0], d[6], d[9], d[10], d[11], d[3], d[7], d[1], d[13], d[12], d[4]};
-                fwrite(r, 8, 12, f);
+                // (d[15]: past tile_load's barrier, in the variant whose stamp 1 is the publishing lane's)
+                const uint64_t r[13] = {d[8], d[0], d[6], d[9], d[10], d[11], d[3], d[7], d[1], d[13], d[12], d[4], d[15]};
+                fwrite(r, 8, 13, f);
             }
             fclose(f);
         }
