@@ -67,6 +67,10 @@ struct sr_core {
     sr_core_log_block_fn log_block;          /* block mode: a batch's whole text in one call       */
     int log_host[2];                         /* the slot's batch could not be staged: the host formats it */
     uint64_t log_device_n, log_host_n;       /* sr_core_device_log_stats                            */
+    int coalesce;                            /* sr_core_set_coalesce: plain counters coalesced on the GPU */
+    const uint8_t *co_text[2];               /* the merged text of the batch being completed in a slot ... */
+    size_t co_base[2];                       /* ... which holds the framed bytes from this offset on       */
+    uint64_t co_totals[4];                   /* sr_core_coalesce_counts                                     */
     int host_fills;                          /* the host changed pending buffers since the last  */
                                              /* submission: upload them with the next one         */
     uint16_t *fill16;
@@ -249,8 +253,10 @@ static void drop_probed(sr_core *c) {
 
 /* Where framed byte `off` of the batch in `slot` lies: in the framed bytes, or, for a slot batch, in its
  * datagram's slot (the datagram there is its framed form: sr_core_submit_slots wrote the missing '\n').
- * A line, and a datagram, is one run of bytes either way. */
+ * A line, and a datagram, is one run of bytes either way. With sr_core_set_coalesce a record past the batch's
+ * bytes is a merged line: it lies in the slot's merged text. */
 static const uint8_t *batch_at(const sr_core *c, int slot, const uint8_t *framed, uint32_t off) {
+    if (c->co_text[slot] && off >= c->co_base[slot]) return c->co_text[slot] + (off - c->co_base[slot]);
     if (!c->slot_n[slot]) return framed + off;
     return sr_slot_addr(c->in[slot], SR_DATA_BUF_SIZE, c->slot_ends[slot], c->slot_n[slot], off);
 }
@@ -343,6 +349,22 @@ static int device_log(sr_core *c, int slot) {
 static void complete(sr_core *c, int slot, const uint8_t *framed, size_t nbytes, const sr_pack_result *r) {
     memcpy(c->probed, r->probed_dead, c->nwords * sizeof(uint64_t));
     drop_probed(c);
+    c->co_text[slot] = NULL;
+    if (c->coalesce) {   /* the merged lines' bytes, behind the batch's own */
+        const uint8_t *text = NULL;
+        size_t len = 0;
+        uint64_t counts[4];
+        const int rc = sr_route_pack_coalesced(c->ctx, slot, &text, &len, counts);
+        if (rc) {   /* (the text of a routed batch always fits: nothing of this batch can be sent) */
+            core_log(c, SR_ERROR, "%s: sr_route_pack_coalesced() failed %s", "udp_read_cb", strerror(-rc));
+            c->host_fills = 1;
+            c->dg_n[slot] = 0;
+            return;
+        }
+        c->co_text[slot] = text;
+        c->co_base[slot] = nbytes;
+        for (int q = 0; q < 4; q++) c->co_totals[q] += counts[q];
+    }
     /* without the TRACE inputs (the slot was not traced) the WARN lines still come, from the sorted
      * records' unrouted tail, in input order */
     if (c->devlog && device_log(c, slot) == 0) {
@@ -624,6 +646,28 @@ int sr_core_set_name_stats(sr_core *c, const sr_stats_config *cfg) {
     if (!c) return -EINVAL;
     if (c->in_flight >= 0) return -EBUSY;
     return sr_set_name_stats(c->ctx, cfg);
+}
+
+int sr_core_set_coalesce(sr_core *c, const sr_coalesce_config *cfg) {
+    if (!c) return -EINVAL;
+    if (c->in_flight >= 0) return -EBUSY;
+    int rc = sr_set_coalesce(c->ctx, cfg);
+    if (rc) return rc;
+    c->coalesce = cfg ? 1 : 0;
+    c->co_text[0] = c->co_text[1] = NULL;
+    /* both slots' text buffers allocated now (an empty batch each; the device's pending bytes carry over) */
+    for (int k = 0; cfg && k < 2; k++) {
+        sr_pack_result r;
+        if ((rc = sr_route_pack_submit(c->ctx, k, NULL, 0, NULL)) || (rc = sr_route_pack_result(c->ctx, k, &r))) return rc;
+    }
+    return 0;
+}
+
+int sr_core_coalesce_counts(sr_core *c, uint64_t totals[4], int reset) {
+    if (!c || !totals) return -EINVAL;
+    memcpy(totals, c->co_totals, sizeof(c->co_totals));
+    if (reset) memset(c->co_totals, 0, sizeof(c->co_totals));
+    return 0;
 }
 
 int sr_core_name_stats(sr_core *c, sr_stats_snapshot **out, int reset) {

@@ -63,6 +63,8 @@ typedef struct sr_config {
                                                 /* to stdout in one write (sr_core_set_device_log); off by default   */
     int dt_name_stats;                          /* SR_NAME_STATS=1: data lines are counted on the GPU and every ping  */
                                                 /* tick logs the hot names (sr_core_set_name_stats); off by default  */
+    int dt_coalesce;                            /* SR_COALESCE=1: plain counters of one name in a batch leave as one  */
+                                                /* line with their sum (sr_core_set_coalesce); off by default         */
     int dt_yield;                               /* full batches per read event before timers run (0: no cap) */
     double dt_yield_s;                          /* seconds per read event before timers run (0: no cap)  */
     /* alive bits published by the health checker to the data threads */

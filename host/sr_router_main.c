@@ -298,8 +298,13 @@ static void log_name_stats(data_thread *d) {
         return;
     }
     if (s->lines[SR_VALID]) {
-        sr_log(SR_INFO, "name_stats: lines=%llu names~%llu hot=%u%s", (unsigned long long)s->lines[SR_VALID],
-               (unsigned long long)(sr_stats_cardinality(s, SR_STATS_ALL) + 0.5), s->n_hot, s->hot_overflow ? "+" : "");
+        char co[64] = "";
+        uint64_t t[4];
+        /* SR_COALESCE=1 too: the lines the coalescing dropped of those it saw since the last ping */
+        if (d->c->dt_coalesce && sr_core_coalesce_counts(d->core, t, 1) == 0)
+            snprintf(co, sizeof(co), " coalesced=%llu/%llu", (unsigned long long)t[1], (unsigned long long)(t[0] + t[1]));
+        sr_log(SR_INFO, "name_stats: lines=%llu names~%llu hot=%u%s%s", (unsigned long long)s->lines[SR_VALID],
+               (unsigned long long)(sr_stats_cardinality(s, SR_STATS_ALL) + 0.5), s->n_hot, s->hot_overflow ? "+" : "", co);
         for (uint32_t i = 0; i < s->n_hot && i < NAME_STATS_HOT_LINES; i++) {
             const sr_stats_hot *h = &s->hot[i];
             sr_log(SR_INFO, "name_stats: hot %.*s lines~%llu",
@@ -391,6 +396,13 @@ void *sr_data_thread(void *arg) {
             return thread_fail(d, 1);
         }
     }
+    if (c->dt_coalesce) {
+        const sr_coalesce_config defaults = {0};
+        if ((rc = sr_core_set_coalesce(d->core, &defaults))) {
+            sr_log(SR_ERROR, "%s: sr_core_set_coalesce() failed %s", fn, strerror(-rc));
+            return thread_fail(d, 1);
+        }
+    }
     d->slot = 0;
     d->batch = sr_core_slot_buffer(d->core, 0, &d->cap);
     d->trace = sr_log_level <= SR_TRACE;
@@ -469,6 +481,8 @@ int main(int argc, char *argv[]) {
     config.dt_device_log = dl && dl[0] == '1';
     const char *ns = getenv("SR_NAME_STATS");
     config.dt_name_stats = ns && ns[0] == '1';
+    const char *co = getenv("SR_COALESCE");
+    config.dt_coalesce = co && co[0] == '1';
     config.dt_yield = dy ? atoi(dy) : 0;
     config.dt_yield_s = dys ? atof(dys) : READ_EVENT_SECONDS;
 

@@ -813,6 +813,109 @@ int sr_stats_merge(sr_stats_snapshot *into, const sr_stats_snapshot *from);
  * Returns 0, -EINVAL, -ENOMEM, -EBUSY (a slot is in flight). */
 int sr_set_name_stats(sr_ctx *ctx, const sr_stats_config *cfg_or_null);
 
+/* ---- plain counters coalesced on the device -------------------------------------------------------- */
+/* When a name is hot, most bytes sent to its downstream are copies of one line `<name>:<n>|c` that differ in a
+ * small integer. This stage adds those integers together before the packets are packed. It consumes what the
+ * route launch leaves on the device (the input-order records and the 64-bit name hashes) and writes a shorter
+ * record list; the merged lines' text is appended to the batch itself, so sr_pack_packets and sr_pack_payloads
+ * run unchanged on the result. Exact and deterministic (tests/coalesce_expect.py restates it); best effort by
+ * construction: every merge made is exact, not every possible merge is made.
+ *
+ * Of a batch the first n = min(*d_n_records, max_records) records are read, d_hashes as given (never recomputed),
+ * and no byte outside [0, nbytes).
+ *
+ * Plain counter: record i = (offset o, length L, route r) with r < n_downstreams, 6 <= L <= 1449,
+ *   o + L <= nbytes, byte o + L - 1 a '\n', a first ':' in [o, o + L - 1) at k with
+ *   1 <= k <= SR_COALESCE_NAME_MAX, and the bytes between that ':' and the '\n' exactly -?[0-9]{1,9}\|c (no '+',
+ *   no tenth digit, no sample rate, no other type, no float, no empty value, no tags, no '\r'). Its name is the
+ *   k bytes before the ':', its value v the decimal number ("-0" and leading zeros are accepted). Every other
+ *   record, hostile ones included, passes through untouched.
+ * Groups: with S slots per batch the slot of plain counter i is fmix64(hash_i) & (S - 1) (fmix64 as in the name
+ *   statistics above). A slot's owner is the plain counter with the lowest index among those of the slot.
+ *   Plain counter i joins its slot's owner o iff hash_i == hash_o, route_i == route_o, k_i == k_o and the name
+ *   bytes are equal (the bytes are compared: sdbm collides, and adding two metrics together would be data
+ *   corruption). A plain counter that does not join passes through untouched. The table is direct mapped: no
+ *   probing, no overflow, no dependence on the order of execution.
+ * Output: the records come out in input order into d_out, each as it was, except in groups of two or more
+ *   members: there the owner becomes {offset = nbytes + a, length = k + 1 + len(dec) + 3, route} and the other
+ *   members are dropped. The merged line is name ':' dec(sum of the group's values) "|c\n" (the sum a signed
+ *   64-bit number; dec has a '-' when negative, no leading zeros, "0" for zero), and `a` is the total length of
+ *   the merged lines of owners earlier in input order. The merged text goes to d_bytes + nbytes + a: the caller
+ *   leaves append_cap bytes of room behind the batch. Of the text the first min(d_counts[3], append_cap) bytes
+ *   are written and nothing at or past append_cap; the text is complete iff d_counts[3] <= append_cap, and only
+ *   then are the merged records' offsets (nbytes + a, 32 bits) usable.
+ *   d_counts: four u64 {records out, records dropped, groups merged, appended bytes needed}; &d_counts[0] is
+ *   what a caller passes on as d_n_records. sr_pack_payloads then takes nbytes + append_cap as its nbytes.
+ * Bounds: a merged line has 6..1449 bytes (hence k >= 1 and k <= 1425 = 1449 - 1 - 20 - 3). A group of c lines
+ *   whose longest value has d digits sums to at most d + digits(c) digits and a sign, and
+ *   1 + digits(c) <= 5 (c - 1) for every c >= 2: a merged line is never longer than its group's lines together.
+ *   So for records that do not overlap (the route launch's never do) the appended bytes never exceed nbytes,
+ *   and SR_COALESCE_APPEND_CAPACITY(nbytes) always suffices. |sum| < 2^60 since nbytes <= 2^30.
+ *
+ * sr_coalesce_config: slots = 0 selects SR_COALESCE_DEFAULT_SLOTS, otherwise a power of two in
+ *   SR_COALESCE_MIN_SLOTS..SR_COALESCE_MAX_SLOTS.
+ * sr_coalesce_open : allocates the tables once, SR_MAX_BATCHES_PER_LAUNCH x slots x 16 bytes (owner u32, members
+ *   u32, sum i64); not inside stream capture. 0, -EINVAL, -ENOMEM, -EBUSY (the stage is open).
+ * sr_coalesce      : count in 1..SR_MAX_BATCHES_PER_LAUNCH batches, asynchronous on the context's stream. Its
+ *   per-record scratch is allocated on the first call or on one with more records (sum of max_records) than
+ *   any before; later calls allocate nothing and can be captured in a graph. -EINVAL before any launch for a
+ *   null required pointer (d_n_records, d_counts, d_hashes; d_recs and d_out with max_records > 0; d_bytes
+ *   with nbytes > 0), d_out == d_recs, nbytes > 2^30, nbytes + append_cap > 0xFFFFFFF0,
+ *   max_records > 0xFFFFFFF0, a bad count or a context whose stage is not open. d_recs and d_out are aligned as
+ *   sr_record (4 bytes), d_hashes and d_counts to 8; d_bytes has any alignment.
+ * sr_coalesce_close: waits for the stream and frees the stage, switch included (sr_close does it too). 0,
+ *   -EINVAL, -EBUSY (a slot is in flight).
+ *
+ * Host only (no GPU):
+ *   sr_coalesce_parse : the plain-counter test on one line of `len` bytes ('\n' included); 1 and *name_len = k,
+ *     *value = v, or 0 (name_len and value may be NULL);
+ *   sr_coalesce_format: writes name ':' dec(sum) "|c\n" to dst (name_len + 24 bytes always suffice) and returns
+ *     its length. */
+#define SR_COALESCE_NAME_MAX       1425u
+#define SR_COALESCE_MIN_SLOTS      16u
+#define SR_COALESCE_MAX_SLOTS      4194304u   /* 2^22 */
+#define SR_COALESCE_DEFAULT_SLOTS  65536u
+#define SR_COALESCE_MAX_BYTES      1073741824u   /* 2^30: a batch's nbytes */
+#define SR_COALESCE_APPEND_CAPACITY(nbytes) (nbytes)
+
+typedef struct sr_coalesce_config {
+    uint32_t slots;
+} sr_coalesce_config;
+
+typedef struct sr_coalesce_batch {
+    uint8_t *d_bytes; size_t nbytes;              /* the routed batch; the merged text goes behind it      */
+    size_t append_cap;                            /* room behind d_bytes + nbytes                          */
+    const sr_record *d_recs;                      /* input-order records (sr_batch.d_out)                  */
+    const uint64_t *d_n_records; size_t max_records;
+    const uint64_t *d_hashes;                     /* max_records u64 (sr_batch.d_hashes); required         */
+    sr_record *d_out;                             /* max_records records; not d_recs                       */
+    uint64_t *d_counts;                           /* 4 u64: out, dropped, groups, appended bytes needed    */
+} sr_coalesce_batch;
+
+int sr_coalesce_open(sr_ctx *ctx, const sr_coalesce_config *cfg);
+int sr_coalesce_close(sr_ctx *ctx);
+int sr_coalesce(sr_ctx *ctx, const sr_coalesce_batch *batches, size_t count);
+int sr_coalesce_parse(const uint8_t *line, size_t len, uint32_t *name_len, int64_t *value);
+size_t sr_coalesce_format(uint8_t *dst, const uint8_t *name, uint32_t name_len, int64_t sum);
+
+/* The coalescing of the host-memory path. With sr_set_coalesce(ctx, cfg) (cfg as sr_coalesce_open takes it; the
+ * stage is opened when it is not yet, and the context's input buffer is allocated again with max_batch_bytes of
+ * room behind it) every later sr_route_pack_submit / sr_route_pack_submit_slots / sr_route_pack_batch runs
+ * sr_coalesce between the route and the packing: the hashes are requested as sr_set_trace requests them, and the
+ * packing and the payloads (sr_set_payloads) work on the coalesced records. `sorted`, `packets`, `fill`,
+ * n_records and n_valid then describe the coalesced batch; records in `sorted` with offset >= nbytes point into
+ * the merged text, at offset - nbytes. The trace (sr_route_pack_trace), the log text and the name statistics keep
+ * the original input-order records, so logs and statistics are byte-identical to the switch being off. NULL
+ * turns the switch off (the stage stays open until sr_coalesce_close, which fails with -EBUSY while a slot is in
+ * flight). Off by default: nothing is allocated, launched or copied.
+ * Returns 0, -EINVAL (max_batch_bytes > 2^30 or 2 * max_batch_bytes > 0xFFFFFFF0, a bad cfg), -ENOMEM, -EBUSY (a
+ * slot is in flight).
+ * sr_route_pack_coalesced: after sr_route_pack_result(slot) (for sr_route_pack_batch: slot 2), a page-locked copy
+ * of the batch's merged text (*len bytes, valid until the slot's next submission) and the stage's four counts.
+ * -EBUSY when the slot is in flight or was submitted with the switch off. */
+int sr_set_coalesce(sr_ctx *ctx, const sr_coalesce_config *cfg_or_null);
+int sr_route_pack_coalesced(sr_ctx *ctx, int slot, const uint8_t **text, size_t *len, uint64_t counts[4]);
+
 /* ---- owner side of the multi-GPU regroup: received lines into packets ------------------------------ */
 /* After sr_regroup_launch / sr_regroup_run the lines of the shards a GPU owns lie in d_recv_bytes /
  * d_recv_recs: every source's chunk in source order 0, 1, ..., each chunk batch 0's lines, then batch

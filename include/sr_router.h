@@ -171,6 +171,19 @@ int sr_core_device_log_stats(const sr_core *core, uint64_t *device_batches, uint
 int sr_core_set_name_stats(sr_core *core, const sr_stats_config *cfg_or_null);
 int sr_core_name_stats(sr_core *core, sr_stats_snapshot **out, int reset);
 
+/* Plain counters coalesced. With sr_core_set_coalesce(core, cfg) (cfg as sr_coalesce_open takes it, sr_route.h:
+ * slots = 0 selects the default) every later batch of sr_core_route*, sr_core_submit* and sr_core_submit_slots is
+ * coalesced on the GPU between the route and the packing (sr_set_coalesce): lines `<name>:<n>|c` of one name in
+ * one batch leave as one line with the sum, at the place of the first of them. Other lines, their order per
+ * downstream, the log lines and the name statistics are those of the switch being off; packets, traffic counters
+ * and pending bytes describe the coalesced lines. Ping lines are not coalesced (sr_core_ping routes them outside
+ * the submit path). NULL turns the switch off.
+ * sr_core_coalesce_counts: the sums over the batches completed since the core was opened or the last reset of
+ * {lines out, lines dropped, groups merged, merged text bytes}; reset != 0 starts them again from zero.
+ * Return 0, -EINVAL, -EBUSY (set: a batch is in flight, drain first), -ENOMEM. */
+int sr_core_set_coalesce(sr_core *core, const sr_coalesce_config *cfg_or_null);
+int sr_core_coalesce_counts(sr_core *core, uint64_t totals[4], int reset);
+
 /* Test hook (fault injection; nothing calls it in the executable): the fail_submit-th call of
  * sr_core_submit* fails as a failed sr_route_pack_submit (the batch is not taken), and the
  * fail_finish-th batch to complete fails as a failed sr_route_pack_result (its packets and log lines

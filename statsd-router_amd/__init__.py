@@ -61,6 +61,8 @@ ABI_FUNCTIONS = (
     "sr_format_log", "sr_set_logtext", "sr_route_pack_set_prefix", "sr_route_pack_set_ends", "sr_route_pack_logtext",
     "sr_stats_open", "sr_stats_update", "sr_stats_reset", "sr_stats_read", "sr_stats_free", "sr_stats_close",
     "sr_name_hash", "sr_stats_estimate", "sr_stats_cardinality", "sr_stats_merge", "sr_set_name_stats",
+    "sr_coalesce_open", "sr_coalesce_close", "sr_coalesce", "sr_coalesce_parse", "sr_coalesce_format",
+    "sr_set_coalesce", "sr_route_pack_coalesced",
 )
 SR_LOG_MAX_PREFIX = 256
 SR_LOG_TRACE, SR_LOG_WARN = 0, 3   # sr_log_batch.min_level and the d_levels values
@@ -186,6 +188,47 @@ STATS_TILE = 1024   # kStatsTile (csrc/stats_kernel.hpp): records per tile of th
 STATS_LDS_SHARDS = 512   # kStatsLdsShards: per-shard sums in LDS up to this many downstreams
 STATS_HOT_DTYPE = np.dtype([("hash", "<u8"), ("lines", "<u8"), ("name_len", "<u4"), ("name", "u1", (108,))])
 assert STATS_HOT_DTYPE.itemsize == 128 == ctypes.sizeof(SrStatsHot)
+
+
+class SrCoalesceConfig(ctypes.Structure):
+    """struct sr_coalesce_config (include/sr_route.h); slots = 0 selects the default."""
+    _fields_ = [("slots", ctypes.c_uint32)]
+
+
+class SrCoalesceBatch(ctypes.Structure):
+    """struct sr_coalesce_batch (include/sr_route.h): one routed batch of sr_coalesce."""
+    _fields_ = [("d_bytes", ctypes.c_void_p), ("nbytes", ctypes.c_size_t), ("append_cap", ctypes.c_size_t),
+                ("d_recs", ctypes.c_void_p), ("d_n_records", ctypes.c_void_p), ("max_records", ctypes.c_size_t),
+                ("d_hashes", ctypes.c_void_p), ("d_out", ctypes.c_void_p), ("d_counts", ctypes.c_void_p)]
+
+
+SR_COALESCE_NAME_MAX = 1425
+SR_COALESCE_MIN_SLOTS = 16
+SR_COALESCE_MAX_SLOTS = 1 << 22
+SR_COALESCE_DEFAULT_SLOTS = 65536
+SR_COALESCE_MAX_BYTES = 1 << 30
+COALESCE_TILE = 256   # kCoalesceTile (csrc/coalesce_kernel.hpp): records per tile of the coalescing kernels
+
+
+def coalesce_append_capacity(nbytes: int) -> int:
+    """SR_COALESCE_APPEND_CAPACITY: room behind a batch that always holds its merged text."""
+    return nbytes
+
+
+def coalesce_parse(line: bytes):
+    """sr_coalesce_parse on one line ('\\n' included): (name_len, value) of a plain counter, else None."""
+    k, v = ctypes.c_uint32(0), ctypes.c_int64(0)
+    buf = (ctypes.c_uint8 * max(len(line), 1)).from_buffer_copy(line or b"\0")
+    return (int(k.value), int(v.value)) if lib().sr_coalesce_parse(buf, len(line), ctypes.byref(k), ctypes.byref(v)) \
+        else None
+
+
+def coalesce_format(name: bytes, total: int) -> bytes:
+    """sr_coalesce_format: the merged line of `name` and the sum `total`."""
+    dst = (ctypes.c_uint8 * (len(name) + 24))()
+    src = (ctypes.c_uint8 * max(len(name), 1)).from_buffer_copy(name or b"\0")
+    n = lib().sr_coalesce_format(dst, src, len(name), total)
+    return bytes(dst[:n])
 
 
 class SrStatsSnapshot(ctypes.Structure):
@@ -440,6 +483,14 @@ def _load_route_lib() -> ctypes.CDLL:
         "sr_stats_cardinality": (ctypes.c_double, [ctypes.POINTER(SrStatsSnapshot), ctypes.c_uint32]),
         "sr_stats_merge": (ctypes.c_int, [ctypes.POINTER(SrStatsSnapshot), ctypes.POINTER(SrStatsSnapshot)]),
         "sr_set_name_stats": (ctypes.c_int, [vp, ctypes.POINTER(SrStatsConfig)]),
+        "sr_coalesce_open": (ctypes.c_int, [vp, ctypes.POINTER(SrCoalesceConfig)]),
+        "sr_coalesce_close": (ctypes.c_int, [vp]),
+        "sr_coalesce": (ctypes.c_int, [vp, ctypes.POINTER(SrCoalesceBatch), ctypes.c_size_t]),
+        "sr_coalesce_parse": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32),
+                                             ctypes.POINTER(ctypes.c_int64)]),
+        "sr_coalesce_format": (ctypes.c_size_t, [vp, vp, ctypes.c_uint32, ctypes.c_int64]),
+        "sr_set_coalesce": (ctypes.c_int, [vp, ctypes.POINTER(SrCoalesceConfig)]),
+        "sr_route_pack_coalesced": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(vp), c_size_p, u64p]),
     }
     for name in ABI_FUNCTIONS:
         if os.environ.get("SR_ROUTE_LIB") and not hasattr(lib, name):
@@ -864,6 +915,43 @@ class Router:
         """sr_set_name_stats: later route_pack submissions also update the name statistics on the device."""
         _check(self._lib.sr_set_name_stats(self._h, ctypes.byref(SrStatsConfig(**cfg)) if on else None),
                "sr_set_name_stats")
+
+    def coalesce_open(self, slots: int = 0) -> None:
+        """sr_coalesce_open: the coalescing stage of this context (slots = 0: the default table size)."""
+        _check(self._lib.sr_coalesce_open(self._h, ctypes.byref(SrCoalesceConfig(slots))), "sr_coalesce_open")
+
+    def coalesce_close(self) -> None:
+        _check(self._lib.sr_coalesce_close(self._h), "sr_coalesce_close")
+
+    @staticmethod
+    def coalesce_batches(batches):
+        """The sr_coalesce_batch array of [(d_bytes, nbytes, append_cap, d_recs, d_n_records, max_records, d_hashes,
+        d_out, d_counts), ...] (raw device addresses; 0 = NULL)."""
+        arr = (SrCoalesceBatch * max(len(batches), 1))()
+        for i, (db, nb, cap, dr, dn, mr, dh, do, dc) in enumerate(batches):
+            arr[i] = SrCoalesceBatch(db or None, nb, cap, dr or None, dn or None, mr, dh or None, do or None, dc or None)
+        return arr
+
+    def coalesce(self, batches) -> None:
+        """sr_coalesce over the batches of one route launch (as coalesce_batches takes them, or its array),
+        asynchronous on the context's stream."""
+        arr = batches if isinstance(batches, ctypes.Array) else self.coalesce_batches(batches)
+        _check(self._lib.sr_coalesce(self._h, arr, len(batches)), "sr_coalesce")
+
+    def set_coalesce(self, on: bool = True, slots: int = 0) -> None:
+        """sr_set_coalesce: later route_pack submissions coalesce plain counters between the route and the
+        packing."""
+        _check(self._lib.sr_set_coalesce(self._h, ctypes.byref(SrCoalesceConfig(slots)) if on else None),
+               "sr_set_coalesce")
+
+    def route_pack_coalesced(self, slot: int):
+        """sr_route_pack_coalesced after route_pack_result(slot) (route_pack: slot 2): (merged text, counts[4])."""
+        text, n = ctypes.c_void_p(), ctypes.c_size_t()
+        counts = (ctypes.c_uint64 * 4)()
+        _check(self._lib.sr_route_pack_coalesced(self._h, slot, ctypes.byref(text), ctypes.byref(n), counts),
+               "sr_route_pack_coalesced")
+        raw = bytes((ctypes.c_uint8 * n.value).from_address(text.value)) if n.value else b""
+        return raw, np.array(list(counts), np.uint64)
 
     def route_pack_submit_slots(self, slot: int, slots, stride: int, lens, fill=None) -> None:
         """sr_route_pack_submit_slots (asynchronous): `slots` is page-locked memory (a HostBuffer, or its

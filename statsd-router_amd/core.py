@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from . import LIB_DIR, SrError, SrStatsConfig, SrStatsSnapshot, StatsSnapshot, _check, alive_words, lib
+from . import LIB_DIR, SrCoalesceConfig, SrError, SrStatsConfig, SrStatsSnapshot, StatsSnapshot, _check, alive_words, lib
 
 ROUTER_LIB = os.path.join(LIB_DIR, "libsr_router.so")
 SR_TRACE, SR_DEBUG, SR_INFO, SR_WARN, SR_ERROR = range(5)
@@ -80,6 +80,10 @@ def router_lib() -> ctypes.CDLL:
         L.sr_core_set_name_stats.argtypes = [vp, ctypes.POINTER(SrStatsConfig)]
         L.sr_core_name_stats.restype = ctypes.c_int
         L.sr_core_name_stats.argtypes = [vp, ctypes.POINTER(ctypes.POINTER(SrStatsSnapshot)), ctypes.c_int]
+        L.sr_core_set_coalesce.restype = ctypes.c_int
+        L.sr_core_set_coalesce.argtypes = [vp, ctypes.POINTER(SrCoalesceConfig)]
+        L.sr_core_coalesce_counts.restype = ctypes.c_int
+        L.sr_core_coalesce_counts.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
         L.sr_core_device_log_stats.restype = ctypes.c_int
         L.sr_core_device_log_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         _RLIB = L
@@ -236,6 +240,17 @@ class Core:
         the defaults)."""
         _check(self._L.sr_core_set_name_stats(self._h, ctypes.byref(SrStatsConfig(**cfg)) if on else None),
                "sr_core_set_name_stats")
+
+    def set_coalesce(self, on: bool = True, slots: int = 0) -> None:
+        """sr_core_set_coalesce: later batches have their plain counters coalesced on the GPU."""
+        _check(self._L.sr_core_set_coalesce(self._h, ctypes.byref(SrCoalesceConfig(slots)) if on else None),
+               "sr_core_set_coalesce")
+
+    def coalesce_counts(self, reset: bool = False):
+        """sr_core_coalesce_counts: [lines out, lines dropped, groups merged, merged text bytes] so far."""
+        t = (ctypes.c_uint64 * 4)()
+        _check(self._L.sr_core_coalesce_counts(self._h, t, 1 if reset else 0), "sr_core_coalesce_counts")
+        return [int(x) for x in t]
 
     def name_stats(self, reset: bool = False) -> StatsSnapshot:
         """sr_core_name_stats: drains, then a copy of the snapshot; reset starts the statistics again."""

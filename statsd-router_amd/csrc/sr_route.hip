@@ -16,6 +16,7 @@
 #include <new>
 
 #include "../../include/sr_route.h"
+#include "coalesce_kernel.hpp"
 #include "exchange.hpp"
 #include "frame_host.hpp"
 #include "frame_kernel.hpp"
@@ -82,6 +83,10 @@ struct sr_ctx {
     uint32_t *d_ends;             // slot submissions at TRACE: the frame kernels' datagram ends (SR_MAX_SLOTS)
     StatsState stats;             // sr_stats_open: the name statistics' device state
     int name_stats;               // sr_set_name_stats: submissions also run sr_stats_update on the device
+    CoalesceState coalesce;       // sr_coalesce_open: the coalescing stage's tables and scratch
+    int coalesce_on;              // sr_set_coalesce: submissions coalesce between the route and the packing
+    sr_record *d_cout;            // ... into these records (one per byte of the largest batch) ...
+    uint64_t *d_ccounts;          // ... and these four counts
     // packing knobs (sr_set_knob): forced chunk lines (0: by shape), XCD-local chunks, chain walked in emit
     uint32_t mtu_chunk;
     int mtu_xcd, mtu_walk;
@@ -110,6 +115,10 @@ struct sr_ctx {
         uint8_t *phost, *pdev;
         size_t pay_cap, poff_cap; // arena bytes; offsets - 1 (descriptors)
         int payloaded;            // the batch in the slot was submitted with payloads on
+        // sr_set_coalesce: merged text | {4 counts, input records} (one more page-locked allocation)
+        uint8_t *chost, *cdev;
+        size_t ctext_cap;
+        int coalesced;            // the batch in the slot was submitted with the coalescing on
         // sr_set_logtext: text | offsets | levels | {total, messages} | staged prefixes | staged ends
         uint8_t *lhost, *ldev;
         size_t ltext_cap, lmsg_cap;
@@ -237,11 +246,17 @@ void sr_close(sr_ctx *c) {
     free_ptr(c->d_log);
     free_ptr(c->d_ends);
     free_ptr(c->stats.d_base);
+    free_ptr(c->coalesce.d_table);
+    free_ptr(c->coalesce.d_scratch);
+    free_ptr(c->coalesce.d_tiles);
+    free_ptr(c->d_cout);
+    free_ptr(c->d_ccounts);
     for (auto &sl : c->slot) {
         if (sl.host) (void)hipHostFree(sl.host);
         if (sl.thost) (void)hipHostFree(sl.thost);
         if (sl.phost) (void)hipHostFree(sl.phost);
         if (sl.lhost) (void)hipHostFree(sl.lhost);
+        if (sl.chost) (void)hipHostFree(sl.chost);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1185,6 +1200,154 @@ static int grow(void **ptr, size_t *cap, size_t need, size_t elem) {
     return 0;
 }
 
+// ---- plain counters coalesced (coalesce_kernel.hpp, coalesce_host.hpp) ------------------------------------
+int sr_coalesce_open(sr_ctx *c, const sr_coalesce_config *cfg) {
+    if (!c) return -EINVAL;
+    CoalesceState &st = c->coalesce;
+    if (st.open) return -EBUSY;
+    uint32_t slots = 0;
+    if (coalesce_resolve(cfg, &slots) != 0) return -EINVAL;
+    (void)hipSetDevice(c->device);
+    if (hipMalloc(&st.d_table, (size_t)kCoalesceMaxBatches * slots * sizeof(CoalesceSlot)) != hipSuccess) {
+        st.d_table = nullptr;
+        (void)hipGetLastError();
+        return -ENOMEM;
+    }
+    st.slots = slots;
+    st.open = 1;
+    return 0;
+}
+
+int sr_coalesce_close(sr_ctx *c) {
+    if (!c) return -EINVAL;
+    CoalesceState &st = c->coalesce;
+    for (int k = 0; k < 3; ++k)
+        if (c->slot[k].busy) return -EBUSY;
+    if (!st.open) return 0;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    free_ptr(st.d_table);
+    free_ptr(st.d_scratch);
+    free_ptr(st.d_tiles);
+    memset(&st, 0, sizeof(st));
+    c->coalesce_on = 0;
+    return 0;
+}
+
+int sr_set_coalesce(sr_ctx *c, const sr_coalesce_config *cfg) {
+    if (!c) return -EINVAL;
+    for (int k = 0; k < 3; ++k)
+        if (c->slot[k].busy) return -EBUSY;
+    if (!cfg) {
+        c->coalesce_on = 0;
+        return 0;
+    }
+    const size_t full = c->ds.max_batch;
+    if (full > SR_COALESCE_MAX_BYTES || 2 * (uint64_t)full > 0xFFFFFFF0ull) return -EINVAL;
+    if (!c->coalesce.open) {
+        const int rc = sr_coalesce_open(c, cfg);
+        if (rc) return rc;
+    }
+    (void)hipSetDevice(c->device);
+    if (!c->d_ccounts) {   // the first time: the input buffer again, with room for the merged text behind a batch
+        (void)hipStreamSynchronize(c->stream);
+        uint8_t *in = nullptr;
+        if (hipMalloc(&in, 2 * full) != hipSuccess) return -ENOMEM;
+        if (hipMalloc(&c->d_ccounts, 4 * sizeof(uint64_t)) != hipSuccess) {
+            c->d_ccounts = nullptr;
+            free_ptr(in);
+            return -ENOMEM;
+        }
+        free_ptr(c->d_in);
+        c->d_in = in;
+    }
+    c->coalesce_on = 1;
+    return 0;
+}
+
+int sr_route_pack_coalesced(sr_ctx *c, int slot, const uint8_t **text, size_t *len, uint64_t counts[4]) {
+    if (!c || !text || !len || !counts || slot < 0 || slot > 2) return -EINVAL;
+    const sr_ctx::Slot &sl = c->slot[slot];
+    if (sl.busy || !sl.coalesced || !sl.chost) return -EBUSY;
+    const uint64_t *hc = (const uint64_t *)(sl.chost + ((sl.ctext_cap + 255) & ~(size_t)255));
+    for (int q = 0; q < 4; ++q) counts[q] = hc[q];
+    *text = sl.chost;
+    *len = (size_t)(hc[3] < sl.ctext_cap ? hc[3] : sl.ctext_cap);
+    return hc[3] > sl.ctext_cap ? -ENOSPC : 0;
+}
+
+int sr_coalesce(sr_ctx *c, const sr_coalesce_batch *batches, size_t count) {
+    static_assert(kCoalesceMaxBatches == (int)SR_MAX_BATCHES_PER_LAUNCH, "launch batch limit");
+    if (!c || !c->coalesce.open || !batches || count == 0 || count > (size_t)kCoalesceMaxBatches) return -EINVAL;
+    CoalesceState &st = c->coalesce;
+    size_t records = 0, tiles = 0;   // the scratch's sizes, by max_records
+    uint64_t grid_tiles = 0;         // the grid's bound only (the kernels number the tiles by the device's counts)
+    for (size_t j = 0; j < count; ++j) {
+        const sr_coalesce_batch &b = batches[j];
+        if (!b.d_n_records || !b.d_counts || !b.d_hashes || (b.nbytes && !b.d_bytes)) return -EINVAL;
+        if (b.max_records && (!b.d_recs || !b.d_out || b.d_out == b.d_recs)) return -EINVAL;
+        if ((const void *)b.d_counts == (const void *)b.d_n_records) return -EINVAL;   // read after the counts are written
+        if (b.nbytes > SR_COALESCE_MAX_BYTES || b.max_records > 0xFFFFFFF0ull) return -EINVAL;
+        if (b.append_cap > 0xFFFFFFF0ull || (uint64_t)b.nbytes + b.append_cap > 0xFFFFFFF0ull) return -EINVAL;
+        records += b.max_records;
+        tiles += (b.max_records + kCoalesceTile - 1) / kCoalesceTile;
+        const uint64_t likely = (uint64_t)b.nbytes / kCoalesceGridLineBytes + 1u;
+        const uint64_t room = b.max_records < likely ? b.max_records : likely;
+        grid_tiles += (room + kCoalesceTile - 1) / kCoalesceTile;
+    }
+    (void)hipSetDevice(c->device);
+    int rc;
+    if ((rc = grow((void **)&st.d_scratch, &st.scratch_cap, records, sizeof(uint2)))) return rc;
+    if ((rc = grow((void **)&st.d_tiles, &st.tiles_cap, tiles, sizeof(uint4)))) return rc;
+    CoalesceArgs a;
+    memset(&a, 0, sizeof(a));
+    size_t at = 0;
+    for (size_t j = 0; j < count; ++j) {
+        const sr_coalesce_batch &b = batches[j];
+        CoalesceBatchArg &o = a.b[j];
+        o.bytes = b.d_bytes;
+        o.recs = b.d_recs;
+        o.n_records = b.d_n_records;
+        o.hashes = b.d_hashes;
+        o.out = b.d_out;
+        o.counts = b.d_counts;
+        o.scratch = st.d_scratch + at;
+        o.append_cap = b.append_cap;
+        o.nbytes = (uint32_t)b.nbytes;
+        o.max_records = (uint32_t)b.max_records;
+        at += b.max_records;
+    }
+    a.table = st.d_table;
+    a.tiles = st.d_tiles;
+    a.nb = (uint32_t)count;
+    a.nds = c->ds.nds;
+    a.slots = st.slots;
+    if (grid_tiles) {
+        const uint64_t entries = (uint64_t)count * st.slots;   // at most 2^27
+        const uint64_t cg = (entries + kCoalesceBlock - 1) / kCoalesceBlock;
+        const dim3 clear_grid((uint32_t)(cg < (uint64_t)kCoalesceGroups ? cg : (uint64_t)kCoalesceGroups));
+        const dim3 grid((uint32_t)(grid_tiles < (uint64_t)kCoalesceGroups ? grid_tiles : (uint64_t)kCoalesceGroups));
+        hipLaunchKernelGGL(coalesce_clear_kernel, clear_grid, dim3(kCoalesceBlock), 0, c->stream, st.d_table, (uint32_t)entries);
+        hipLaunchKernelGGL(coalesce_claim_kernel, grid, dim3(kCoalesceBlock), 0, c->stream, a);
+        hipLaunchKernelGGL(coalesce_join_kernel, grid, dim3(kCoalesceBlock), 0, c->stream, a);
+        hipLaunchKernelGGL(coalesce_sum_kernel, grid, dim3(kCoalesceBlock), 0, c->stream, a);
+        hipLaunchKernelGGL(coalesce_scan_kernel, dim3((uint32_t)count), dim3(kCoalesceScanBlock), 0, c->stream, a);
+        hipLaunchKernelGGL(coalesce_emit_kernel, grid, dim3(kCoalesceBlock), 0, c->stream, a);
+    } else {   // no batch has room for a record: the counts alone
+        hipLaunchKernelGGL(coalesce_scan_kernel, dim3((uint32_t)count), dim3(kCoalesceScanBlock), 0, c->stream, a);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+int sr_coalesce_parse(const uint8_t *line, size_t len, uint32_t *name_len, int64_t *value) {
+    return coalesce_parse_line(line, len, name_len, value);
+}
+
+size_t sr_coalesce_format(uint8_t *dst, const uint8_t *name, uint32_t name_len, int64_t sum) {
+    if (!dst || (name_len && !name)) return 0;
+    return coalesce_format_line(dst, name, name_len, sum);
+}
+
 // Host outputs of a slot for batches of up to nbytes (grown, never shrunk; the slot is idle).
 static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static int slot_reserve(sr_ctx *c, int k, size_t nbytes) {
@@ -1268,6 +1431,25 @@ static int slot_payload_reserve(sr_ctx *c, int k, size_t nbytes) {
     return 0;
 }
 
+// sr_set_coalesce: the slot's merged text and counts (grown, never shrunk; the slot is idle): text | 5 u64
+static int slot_coalesce_reserve(sr_ctx *c, int k, size_t nbytes) {
+    sr_ctx::Slot &sl = c->slot[k];
+    if (sl.chost && nbytes <= sl.ctext_cap) return 0;
+    if (sl.chost) (void)hipHostFree(sl.chost);
+    sl.chost = sl.cdev = nullptr;
+    sl.ctext_cap = 0;
+    void *h = nullptr, *d = nullptr;
+    if (hipHostMalloc(&h, up256(nbytes) + 256, hipHostMallocMapped) != hipSuccess) return -ENOMEM;
+    if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
+        (void)hipHostFree(h);
+        return -EIO;
+    }
+    sl.chost = (uint8_t *)h;
+    sl.cdev = (uint8_t *)d;
+    sl.ctext_cap = nbytes;
+    return 0;
+}
+
 // sr_set_logtext: the slot's text arena, index, totals and the staging of prefixes and ends (sized by the
 // switch, which only changes while every slot is idle)
 struct LogLayout {
@@ -1336,6 +1518,8 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
     if (c->trace && (rc = slot_trace_reserve(c, k, full))) return rc;
     if (c->payloads && (rc = slot_payload_reserve(c, k, full))) return rc;
     if (c->logtext && (rc = slot_log_reserve(c, k))) return rc;
+    const bool coalesce = c->coalesce_on != 0;
+    if (coalesce && (rc = slot_coalesce_reserve(c, k, full))) return rc;
     const bool log_trace = c->logtext && c->log_level == 0;   // the formatter needs hashes and datagram ends
     if (log_trace && src && !c->d_ends && hipMalloc(&c->d_ends, (size_t)SR_MAX_SLOTS * sizeof(uint32_t)) != hipSuccess) {
         c->d_ends = nullptr;
@@ -1381,14 +1565,30 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
         // up to 1024 the probes note the dead shards themselves
         // TRACE (sr_set_trace) needs every line's hash too (sr-main.c:91), and so do the name statistics
         uint64_t *hashes = nullptr;
-        if (c->trace || log_trace || c->name_stats || c->ds.replay_wants_hashes()) {
+        if (c->trace || log_trace || c->name_stats || coalesce || c->ds.replay_wants_hashes()) {
             if ((rc = grow((void **)&c->d_hash, &c->d_hash_cap, full, sizeof(uint64_t)))) return rc;
             hashes = c->d_hash;
         }
         const sr_batch rb{c->d_in, nbytes, c->d_out, cap, hashes, c->d_count, c->d_probed};
-        const sr_pack_batch pb{c->d_out, c->d_count, cap, f_in, c->d_probed, c->d_sorted, c->d_packets, pcap,
-                               c->d_mcounts, f_out};
-        if ((rc = route_pack_impl(c, &rb, &pb, 1))) return rc;
+        if (!coalesce) {
+            const sr_pack_batch pb{c->d_out, c->d_count, cap, f_in, c->d_probed, c->d_sorted, c->d_packets, pcap,
+                                   c->d_mcounts, f_out};
+            if ((rc = route_pack_impl(c, &rb, &pb, 1))) return rc;
+        } else {   // route, coalesce, pack: the packing reads the coalesced records and their count
+            if (!c->d_cout && hipMalloc(&c->d_cout, full * sizeof(sr_record)) != hipSuccess) {
+                c->d_cout = nullptr;
+                return -ENOMEM;
+            }
+            RouteParams p = c->ds.params();
+            DeviceState::add_batch(p, rb.d_bytes, rb.nbytes, rb.d_out, rb.max_records, rb.d_hashes, rb.d_n_records,
+                                   rb.d_probed_dead);
+            if ((rc = launch_variant(c->ds, p, c->stream))) return rc;
+            const sr_coalesce_batch cb{c->d_in, nbytes, nbytes, c->d_out, c->d_count, cap, c->d_hash, c->d_cout, c->d_ccounts};
+            if ((rc = sr_coalesce(c, &cb, 1))) return rc;
+            const sr_pack_batch pb{c->d_cout, c->d_ccounts, cap, f_in, c->d_probed, c->d_sorted, c->d_packets, pcap,
+                                   c->d_mcounts, f_out};
+            if ((rc = pack_many_impl(c, &pb, 1, nullptr, nullptr))) return rc;
+        }
     }
     c->fill_cur ^= 1;
     PackOut o;
@@ -1409,8 +1609,10 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
     sl.framed = src != nullptr;
     sl.frame_bytes = nbytes;
     sl.traced = c->trace;
-    o.recs = (c->trace && nbytes) ? c->d_out : nullptr;   // input order, and the hashes (sr_route_pack_trace)
-    o.hashes = (c->trace && nbytes) ? c->d_hash : nullptr;
+    // input order, and the hashes (sr_route_pack_trace); with the coalescing on coalesce_out_kernel copies them,
+    // by the input's count
+    o.recs = (c->trace && nbytes && !coalesce) ? c->d_out : nullptr;
+    o.hashes = (c->trace && nbytes && !coalesce) ? c->d_hash : nullptr;
     o.h_recs = c->trace ? (sr_record *)sl.tdev : nullptr;
     o.h_hashes = c->trace ? (uint64_t *)(sl.tdev + up256(sl.trec_cap * sizeof(sr_record))) : nullptr;
     // one workgroup per 512 records (two per thread), at most 1024 workgroups (grid-stride beyond)
@@ -1418,10 +1620,33 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
     hipLaunchKernelGGL(pack_out_kernel, dim3((uint32_t)(want < 1024 ? (want ? want : 1) : 1024)), dim3(256), 0,
                        c->stream, o);
     if (hipGetLastError() != hipSuccess) return -EIO;
+    sl.coalesced = coalesce;
+    if (coalesce) {   // the merged text, the counts and the input's record count into the slot's page-locked memory
+        uint64_t *const hc = (uint64_t *)(sl.chost + up256(sl.ctext_cap));
+        if (nbytes == 0) {
+            for (int q = 0; q < 5; ++q) hc[q] = 0;   // the slot is idle: nothing is in flight that writes here
+        } else {
+            CoalesceOut co;
+            co.text = c->d_in + nbytes;
+            co.counts = c->d_ccounts;
+            co.n_records = c->d_count;
+            co.text_cap = nbytes < sl.ctext_cap ? nbytes : sl.ctext_cap;
+            co.rec_cap = c->trace ? sl.trec_cap : 0;
+            co.h_text = sl.cdev;
+            co.h_counts = (uint64_t *)(sl.cdev + up256(sl.ctext_cap));
+            co.recs = c->trace ? c->d_out : nullptr;
+            co.hashes = c->trace ? c->d_hash : nullptr;
+            co.h_recs = c->trace ? (sr_record *)sl.tdev : nullptr;
+            co.h_hashes = c->trace ? (uint64_t *)(sl.tdev + up256(sl.trec_cap * sizeof(sr_record))) : nullptr;
+            hipLaunchKernelGGL(coalesce_out_kernel, dim3((uint32_t)(want < 1024 ? (want ? want : 1) : 1024)),
+                               dim3(kCoalesceBlock), 0, c->stream, co);
+            if (hipGetLastError() != hipSuccess) return -EIO;
+        }
+    }
     sl.payloaded = c->payloads;
     if (c->payloads) {   // the packets' bytes straight into the slot's page-locked memory; the host holds the carries
         const size_t o_off = up256(sl.pay_cap), o_tot = o_off + up256((sl.poff_cap + 1) * sizeof(uint32_t));
-        const sr_payload_batch yb{c->d_in, nbytes, c->d_sorted, nbytes ? cap : 0, c->d_packets, pcap < sl.poff_cap ? pcap : sl.poff_cap,
+        const sr_payload_batch yb{c->d_in, coalesce ? 2 * nbytes : nbytes, c->d_sorted, nbytes ? cap : 0, c->d_packets, pcap < sl.poff_cap ? pcap : sl.poff_cap,
                                   c->d_mcounts, f_out, nullptr, nullptr, sl.pdev, sl.pay_cap,
                                   (uint32_t *)(sl.pdev + o_off), (uint64_t *)(sl.pdev + o_tot)};
         if ((rc = payloads_impl(c, &yb, 1))) return rc;
@@ -1481,7 +1706,8 @@ int sr_route_pack_trace(sr_ctx *c, int slot, const sr_record **records, const ui
     if (!c || !records || !hashes || !n || slot < 0 || slot > 2) return -EINVAL;
     const sr_ctx::Slot &sl = c->slot[slot];
     if (sl.busy || !sl.traced || !sl.thost || !sl.counts) return -EBUSY;
-    const uint64_t nr = sl.counts[2];
+    // the input's records: with the coalescing on counts[2] is the coalesced batch's
+    const uint64_t nr = (sl.coalesced && sl.chost) ? ((const uint64_t *)(sl.chost + up256(sl.ctext_cap)))[4] : sl.counts[2];
     *n = (size_t)(nr < sl.trec_cap ? nr : sl.trec_cap);
     *records = (const sr_record *)sl.thost;
     *hashes = (const uint64_t *)(sl.thost + up256(sl.trec_cap * sizeof(sr_record)));
