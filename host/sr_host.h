@@ -65,6 +65,8 @@ typedef struct sr_config {
                                                 /* tick logs the hot names (sr_core_set_name_stats); off by default  */
     int dt_coalesce;                            /* SR_COALESCE=1: plain counters of one name in a batch leave as one  */
                                                 /* line with their sum (sr_core_set_coalesce); off by default         */
+    const sr_rules_config *dt_name_rules;       /* SR_NAME_RULES=<path>: the rule file read at start; data lines that */
+                                                /* the set drops are not forwarded (sr_core_set_name_rules); off by default */
     int dt_yield;                               /* full batches per read event before timers run (0: no cap) */
     double dt_yield_s;                          /* seconds per read event before timers run (0: no cap)  */
     /* alive bits published by the health checker to the data threads */

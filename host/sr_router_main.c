@@ -287,6 +287,47 @@ static void flush_timer_cb(struct ev_loop *loop, ev_periodic *p, int revents) {
     sr_core_flush_timer(d->core);
 }
 
+/* SR_NAME_RULES=<path>: what the rules dropped since the thread's last ping and the three rules with the most
+ * hits, then the hits start again. */
+static void log_name_rules(data_thread *d) {
+    const sr_rules_config *cfg = d->c->dt_name_rules;
+    static __thread sr_rule_hits hits[SR_RULES_MAX + 1];
+    const int n = sr_core_name_rule_hits(d->core, hits, SR_RULES_MAX + 1, 1);
+    if (n < 0) {
+        sr_log(SR_ERROR, "%s: sr_core_name_rule_hits() failed %s", "ping_cb", strerror(-n));
+        return;
+    }
+    uint64_t lines = 0, bytes = 0;
+    int top[3] = {-1, -1, -1};
+    for (int i = 0; i < n; i++) {
+        const uint32_t action = (uint32_t)i < cfg->n_rules ? cfg->rules[i].action : cfg->default_action;
+        if (action == SR_RULE_DROP) {
+            lines += hits[i].lines;
+            bytes += hits[i].bytes;
+        }
+        if ((uint32_t)i >= cfg->n_rules || !hits[i].lines) continue;
+        int at = i;
+        for (int q = 0; q < 3; q++)   /* insertion into the three best, the earlier rule first among equals */
+            if (top[q] < 0 || hits[at].lines > hits[top[q]].lines) {
+                const int t = top[q];
+                top[q] = at;
+                at = t;
+                if (at < 0) break;
+            }
+    }
+    char text[3 * (SR_RULES_PATTERN_MAX + 40)] = "";
+    size_t used = 0;
+    for (int q = 0; q < 3 && top[q] >= 0; q++) {
+        const sr_rule *r = &cfg->rules[top[q]];
+        used += (size_t)snprintf(text + used, sizeof(text) - used, " %s %.*s%s=%llu", r->action == SR_RULE_DROP ? "drop" : "keep",
+                                 (int)r->len, (const char *)r->pattern, r->kind == SR_RULE_PREFIX ? "*" : "",
+                                 (unsigned long long)hits[top[q]].lines);
+        if (used >= sizeof(text)) break;
+    }
+    sr_log(SR_INFO, "name_rules: dropped lines=%llu bytes=%llu top:%s", (unsigned long long)lines, (unsigned long long)bytes,
+           text[0] ? text : " none");
+}
+
 /* SR_NAME_STATS=1: what the thread routed since its last ping, then the statistics start again. A thread that
  * routed no valid line logs nothing. */
 #define NAME_STATS_HOT_LINES 8
@@ -323,6 +364,7 @@ static void ping_timer_cb(struct ev_loop *loop, ev_periodic *p, int revents) {
     int rc = sr_core_ping(d->core);
     if (rc) sr_log(SR_ERROR, "%s: sr_core_ping() failed %s", "ping_cb", strerror(-rc));
     if (d->c->dt_name_stats) log_name_stats(d);
+    if (d->c->dt_name_rules) log_name_rules(d);
 }
 
 /* a data thread that cannot route: the process ends (status 1) unless SR_REQUIRE_GPU=0 */
@@ -396,6 +438,10 @@ void *sr_data_thread(void *arg) {
             return thread_fail(d, 1);
         }
     }
+    if (c->dt_name_rules && (rc = sr_core_set_name_rules(d->core, c->dt_name_rules))) {
+        sr_log(SR_ERROR, "%s: sr_core_set_name_rules() failed %s", fn, strerror(-rc));
+        return thread_fail(d, 1);
+    }
     if (c->dt_coalesce) {
         const sr_coalesce_config defaults = {0};
         if ((rc = sr_core_set_coalesce(d->core, &defaults))) {
@@ -457,6 +503,34 @@ static void on_sigint(struct ev_loop *loop, ev_signal *w, int revents) {
     _exit(0);
 }
 
+/* the rule file's bytes through sr_rules_parse_text; -errno for a file that cannot be read */
+static int load_name_rules(const char *path, sr_rules_config **out, size_t *bad_line) {
+    FILE *f = fopen(path, "rb");
+    if (!f) return -errno;
+    char *text = NULL;
+    size_t len = 0, cap = 0;
+    for (;;) {
+        if (len == cap) {
+            cap = cap ? 2 * cap : 4096;
+            char *t = realloc(text, cap);
+            if (!t) {
+                free(text);
+                fclose(f);
+                return -ENOMEM;
+            }
+            text = t;
+        }
+        const size_t got = fread(text + len, 1, cap - len, f);
+        len += got;
+        if (got == 0) break;
+    }
+    const int err = ferror(f) ? -EIO : 0;
+    fclose(f);
+    const int rc = err ? err : sr_rules_parse_text(text, len, out, bad_line);
+    free(text);
+    return rc;
+}
+
 int main(int argc, char *argv[]) {
     if (argc != 2) {
         fprintf(stdout, "Usage: %s config.file\n", argv[0]);
@@ -483,6 +557,23 @@ int main(int argc, char *argv[]) {
     config.dt_name_stats = ns && ns[0] == '1';
     const char *co = getenv("SR_COALESCE");
     config.dt_coalesce = co && co[0] == '1';
+    const char *nr = getenv("SR_NAME_RULES");
+    if (nr && nr[0]) {   /* an unreadable or invalid rule file is a config error */
+        sr_rules_config *rules = NULL;
+        size_t bad_line = 0;
+        const int rc = load_name_rules(nr, &rules, &bad_line);
+        if (rc == -EINVAL && bad_line) {
+            sr_log(SR_ERROR, "%s: SR_NAME_RULES %s: line %zu is not a rule", "main", nr, bad_line);
+            exit(1);
+        }
+        if (rc) {
+            sr_log(SR_ERROR, "%s: SR_NAME_RULES %s: %s", "main", nr, strerror(-rc));
+            exit(1);
+        }
+        sr_log(SR_INFO, "%s: name_rules: %u rules, default %s", "main", rules->n_rules,
+               rules->default_action == SR_RULE_DROP ? "drop" : "keep");
+        config.dt_name_rules = rules;   /* lives as long as the process */
+    }
     config.dt_yield = dy ? atoi(dy) : 0;
     config.dt_yield_s = dys ? atof(dys) : READ_EVENT_SECONDS;
 

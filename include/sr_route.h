@@ -916,6 +916,124 @@ size_t sr_coalesce_format(uint8_t *dst, const uint8_t *name, uint32_t name_len, 
 int sr_set_coalesce(sr_ctx *ctx, const sr_coalesce_config *cfg_or_null);
 int sr_route_pack_coalesced(sr_ctx *ctx, int slot, const uint8_t **text, size_t *len, uint64_t counts[4]);
 
+/* ---- name rules on the device: drop or keep metrics by name and prefix ----------------------------- */
+/* A block list or an allow list for a router that fronts a shared statsd tier. The stage sits between the route
+ * launch and the packing (or sr_coalesce): it consumes the input-order records, and the hashes when given, and
+ * writes a shorter record list; sr_pack_packets, sr_pack_payloads and sr_coalesce run unchanged on the result.
+ * Exact and deterministic (tests/rules_expect.py restates it).
+ *
+ * Rule set: n_rules rules, 0 <= n_rules <= SR_RULES_MAX, and a default action. A rule is {pattern, len, kind,
+ *   action}: kind SR_RULE_PREFIX or SR_RULE_EXACT, action SR_RULE_DROP or SR_RULE_KEEP, the pattern 1 to
+ *   SR_RULES_PATTERN_MAX bytes of any value except ':' and '\n' (NUL and high bytes are allowed). The patterns of
+ *   a set hold at most SR_RULES_TEXT_MAX bytes together. Two rules of the same kind and bytes are -EINVAL. A
+ *   default action of SR_RULE_DROP makes the set an allow list.
+ * Subject records: a record (o, L, r) is subject to the rules iff r < n_downstreams, L >= 1 and
+ *   o + L <= nbytes. Every other record (invalid lines, all-dead lines, hostile records) passes through
+ *   untouched and unmatched. No byte outside [0, nbytes) is ever read.
+ * Match, on bytes only: a PREFIX rule of length p matches iff p <= L - 1 and bytes [o, o + p) equal the pattern.
+ *   An EXACT rule matches iff p + 1 <= L - 1, bytes [o, o + p) equal the pattern and byte o + p is ':'. A pattern
+ *   holds no ':', so for a routed line a match implies that the first ':' is at or behind p: a PREFIX match is a
+ *   prefix of the name and an EXACT match is the whole name. No name length is needed.
+ * Which rule wins: the longest matching pattern; between an EXACT and a PREFIX rule of one text the EXACT one.
+ *   The order of the rules does not matter. No match gives the default action; its index is n_rules.
+ * Output: d_out receives the records whose action is KEEP and those that are not subject, in input order. When
+ *   d_hashes and d_hashes_out are both given the hashes are compacted alongside (so sr_coalesce can follow).
+ *   The optional d_match (u16 per input record) receives the winning rule's index: n_rules for the default,
+ *   SR_RULES_NOT_SUBJECT for a record that is not subject. d_counts: four u64 {records out, records dropped,
+ *   bytes dropped, subject records}; &d_counts[0] is what the next stage takes as d_n_records. Of a batch the
+ *   first min(*d_n_records, max_records) records are read.
+ * Hits: the context keeps {lines, bytes} as u64 per rule and for the default, n_rules + 1 pairs, accumulated
+ *   over all calls since sr_rules_open or the last sr_rules_reset.
+ *
+ * sr_rules_open : compiles and uploads the set; not inside stream capture. 0, -EINVAL (a bad set, or the
+ *   context's stream is capturing), -EBUSY (the stage is open), -ENOMEM.
+ * sr_rules      : count in 1..SR_MAX_BATCHES_PER_LAUNCH batches, asynchronous on the context's stream. Its
+ *   scratch is allocated on the first call or on one with more records (sum of max_records) than any before;
+ *   later calls allocate nothing and can be captured in a graph. -EINVAL before any launch for a null required
+ *   pointer (d_n_records, d_counts; d_recs and d_out with max_records > 0; d_bytes with nbytes > 0),
+ *   d_out == d_recs, d_hashes_out == d_hashes (when given), d_counts == d_n_records, nbytes > 0xFFFFFFF0,
+ *   max_records > 0xFFFFFFF0, a bad count or a context whose stage is not open. d_recs and d_out are aligned as
+ *   sr_record (4 bytes), d_hashes, d_hashes_out and d_counts to 8, d_match to 2; d_bytes has any alignment.
+ * sr_rules_read : waits for the stream and copies the first min(n, n_rules + 1) pairs of hits (the default's is
+ *   the last, at n_rules); returns how many it copied, or -EINVAL.
+ * sr_rules_reset: zeroes the hits, in stream order.
+ * sr_rules_close: waits for the stream and frees the stage, switch included (sr_close does it too). 0, -EINVAL,
+ *   -EBUSY (a slot is in flight).
+ *
+ * Host only (no GPU):
+ *   sr_rules_check     : 0 or -EINVAL for a set, as sr_rules_open judges it;
+ *   sr_rules_match     : the winning rule's index for one line of `len` bytes ('\n' included; len = 0 and
+ *     len = 1 match nothing), n_rules for the default, -EINVAL for a bad set or a null line;
+ *   sr_rules_parse_text: the rule file's format into a config that the caller frees with sr_rules_free. One rule
+ *     per line: `drop <pattern>` or `keep <pattern>` for an exact name, a trailing `*` marks a prefix;
+ *     `default drop` or `default keep` sets the default (at most once; keep without it); a line that begins
+ *     with `#` is a comment and empty lines are skipped. The pattern is every byte after the single space up to
+ *     the end of the line, so it may hold spaces, '#' and a '\r'. An exact name that ends in `*` cannot be
+ *     written in the file (the C structure can express it). On error -EINVAL and *err_line = the 1-based line
+ *     at fault: an unknown word, a missing or bad pattern, a duplicate (the second of the two), too many rules
+ *     or too many pattern bytes. */
+#define SR_RULES_MAX          256u
+#define SR_RULES_PATTERN_MAX  64u
+#define SR_RULES_TEXT_MAX     4096u
+#define SR_RULES_NOT_SUBJECT  0xFFFFu
+#define SR_RULE_PREFIX        0u
+#define SR_RULE_EXACT         1u
+#define SR_RULE_DROP          0u
+#define SR_RULE_KEEP          1u
+
+typedef struct sr_rule {
+    const uint8_t *pattern;
+    uint32_t len;
+    uint8_t kind;       /* SR_RULE_PREFIX, SR_RULE_EXACT */
+    uint8_t action;     /* SR_RULE_DROP, SR_RULE_KEEP    */
+} sr_rule;
+
+typedef struct sr_rules_config {
+    const sr_rule *rules;
+    uint32_t n_rules;
+    uint32_t default_action;
+} sr_rules_config;
+
+typedef struct sr_rules_batch {
+    const uint8_t *d_bytes; size_t nbytes;        /* the routed batch                                      */
+    const sr_record *d_recs;                      /* input-order records (sr_batch.d_out)                  */
+    const uint64_t *d_n_records; size_t max_records;
+    sr_record *d_out;                             /* max_records records; not d_recs                       */
+    const uint64_t *d_hashes;                     /* optional: max_records u64 (sr_batch.d_hashes) ...     */
+    uint64_t *d_hashes_out;                       /* ... compacted into these, when both are given         */
+    uint16_t *d_match;                            /* optional: max_records u16, the winning rule's index   */
+    uint64_t *d_counts;                           /* 4 u64: out, dropped, bytes dropped, subject           */
+} sr_rules_batch;
+
+typedef struct sr_rule_hits {
+    uint64_t lines, bytes;
+} sr_rule_hits;
+
+int sr_rules_open(sr_ctx *ctx, const sr_rules_config *cfg);
+int sr_rules_close(sr_ctx *ctx);
+int sr_rules(sr_ctx *ctx, const sr_rules_batch *batches, size_t count);
+int sr_rules_read(sr_ctx *ctx, sr_rule_hits *hits, size_t n);
+int sr_rules_reset(sr_ctx *ctx);
+int sr_rules_check(const sr_rules_config *cfg);
+int sr_rules_match(const sr_rules_config *cfg, const uint8_t *line, size_t len);
+int sr_rules_parse_text(const char *text, size_t len, sr_rules_config **out, size_t *err_line);
+void sr_rules_free(sr_rules_config *cfg);
+
+/* The name rules of the host-memory path. With sr_set_name_rules(ctx, cfg) (the stage is opened with cfg; an
+ * open stage is closed first, hits included) every later sr_route_pack_submit / sr_route_pack_submit_slots /
+ * sr_route_pack_batch runs the route launch, then sr_rules, then sr_coalesce when sr_set_coalesce is on, then the
+ * packing, in place of the fused route and pack. Rules run before the coalescing, so dropped lines are never
+ * merged. `sorted`, `packets`, `fill`, n_records and n_valid then describe the kept lines. The trace
+ * (sr_route_pack_trace), the log text and the name statistics keep the original records: logs and statistics are
+ * byte-identical to the switch being off, and a muted name stays visible among the hot names. NULL turns the
+ * switch off (the stage and its hits stay until sr_rules_close). Off by default: nothing is allocated, launched
+ * or copied.
+ * Returns 0, -EINVAL (a bad set), -ENOMEM, -EBUSY (a slot is in flight).
+ * sr_route_pack_rules: after sr_route_pack_result(slot) (for sr_route_pack_batch: slot 2), the batch's four
+ * counts. -EBUSY when the slot is in flight or was submitted with the switch off. */
+int sr_set_name_rules(sr_ctx *ctx, const sr_rules_config *cfg_or_null);
+int sr_route_pack_rules(sr_ctx *ctx, int slot, uint64_t counts[4]);
+
 /* ---- owner side of the multi-GPU regroup: received lines into packets ------------------------------ */
 /* After sr_regroup_launch / sr_regroup_run the lines of the shards a GPU owns lie in d_recv_bytes /
  * d_recv_recs: every source's chunk in source order 0, 1, ..., each chunk batch 0's lines, then batch

@@ -184,6 +184,21 @@ int sr_core_name_stats(sr_core *core, sr_stats_snapshot **out, int reset);
 int sr_core_set_coalesce(sr_core *core, const sr_coalesce_config *cfg_or_null);
 int sr_core_coalesce_counts(sr_core *core, uint64_t totals[4], int reset);
 
+/* Name rules. With sr_core_set_name_rules(core, cfg) (cfg as sr_rules_open takes it, sr_route.h) every later batch
+ * of sr_core_route*, sr_core_submit* and sr_core_submit_slots has the lines that the set drops taken out on the
+ * GPU between the route and the packing, before the coalescing when that switch is on too (sr_set_name_rules).
+ * The kept lines, their order per downstream, the log lines and the name statistics are those of the switch being
+ * off (a muted name stays visible among the hot names); packets, traffic counters and pending bytes describe the
+ * kept lines. Ping lines are not subject to the rules (sr_core_ping routes them outside the submit path). NULL
+ * turns the switch off. A new set replaces the old one and starts the hits again from zero.
+ * sr_core_name_rule_hits: drains first, then copies the first min(n, n_rules + 1) pairs {lines, bytes} per rule
+ * (the default's is the last, at n_rules) since the set was given or the last reset, and returns how many it
+ * copied; reset != 0 starts them again from zero.
+ * Return 0 (hits: the count), -EINVAL (also: hits before the switch was ever on), -EBUSY (set: a batch is in
+ * flight, drain first), -ENOMEM, -EIO. */
+int sr_core_set_name_rules(sr_core *core, const sr_rules_config *cfg_or_null);
+int sr_core_name_rule_hits(sr_core *core, sr_rule_hits *hits, size_t n, int reset);
+
 /* Test hook (fault injection; nothing calls it in the executable): the fail_submit-th call of
  * sr_core_submit* fails as a failed sr_route_pack_submit (the batch is not taken), and the
  * fail_finish-th batch to complete fails as a failed sr_route_pack_result (its packets and log lines

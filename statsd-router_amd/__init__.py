@@ -63,6 +63,8 @@ ABI_FUNCTIONS = (
     "sr_name_hash", "sr_stats_estimate", "sr_stats_cardinality", "sr_stats_merge", "sr_set_name_stats",
     "sr_coalesce_open", "sr_coalesce_close", "sr_coalesce", "sr_coalesce_parse", "sr_coalesce_format",
     "sr_set_coalesce", "sr_route_pack_coalesced",
+    "sr_rules_open", "sr_rules_close", "sr_rules", "sr_rules_read", "sr_rules_reset", "sr_rules_check", "sr_rules_match",
+    "sr_rules_parse_text", "sr_rules_free", "sr_set_name_rules", "sr_route_pack_rules",
 )
 SR_LOG_MAX_PREFIX = 256
 SR_LOG_TRACE, SR_LOG_WARN = 0, 3   # sr_log_batch.min_level and the d_levels values
@@ -229,6 +231,84 @@ def coalesce_format(name: bytes, total: int) -> bytes:
     src = (ctypes.c_uint8 * max(len(name), 1)).from_buffer_copy(name or b"\0")
     n = lib().sr_coalesce_format(dst, src, len(name), total)
     return bytes(dst[:n])
+
+
+class SrRule(ctypes.Structure):
+    """struct sr_rule (include/sr_route.h)."""
+    _fields_ = [("pattern", ctypes.c_void_p), ("len", ctypes.c_uint32), ("kind", ctypes.c_uint8), ("action", ctypes.c_uint8)]
+
+
+class SrRulesConfig(ctypes.Structure):
+    """struct sr_rules_config (include/sr_route.h)."""
+    _fields_ = [("rules", ctypes.POINTER(SrRule)), ("n_rules", ctypes.c_uint32), ("default_action", ctypes.c_uint32)]
+
+
+class SrRulesBatch(ctypes.Structure):
+    """struct sr_rules_batch (include/sr_route.h): one routed batch of sr_rules."""
+    _fields_ = [("d_bytes", ctypes.c_void_p), ("nbytes", ctypes.c_size_t), ("d_recs", ctypes.c_void_p),
+                ("d_n_records", ctypes.c_void_p), ("max_records", ctypes.c_size_t), ("d_out", ctypes.c_void_p),
+                ("d_hashes", ctypes.c_void_p), ("d_hashes_out", ctypes.c_void_p), ("d_match", ctypes.c_void_p),
+                ("d_counts", ctypes.c_void_p)]
+
+
+class SrRuleHits(ctypes.Structure):
+    """struct sr_rule_hits (include/sr_route.h)."""
+    _fields_ = [("lines", ctypes.c_uint64), ("bytes", ctypes.c_uint64)]
+
+
+SR_RULES_MAX = 256
+SR_RULES_PATTERN_MAX = 64
+SR_RULES_TEXT_MAX = 4096
+SR_RULES_NOT_SUBJECT = 0xFFFF
+SR_RULE_PREFIX, SR_RULE_EXACT = 0, 1
+SR_RULE_DROP, SR_RULE_KEEP = 0, 1
+RULES_TILE = 256   # kRulesTile (csrc/rules_kernel.hpp): records per tile of the rules kernels
+
+
+class RuleSet:
+    """A sr_rules_config and the memory it points into. `rules` is [(pattern bytes, kind, action), ...]."""
+
+    def __init__(self, rules=(), default_action: int = SR_RULE_KEEP):
+        self.rules = [(bytes(p), int(k), int(a)) for p, k, a in rules]
+        self.default_action = int(default_action)
+        self._keep = [(ctypes.c_uint8 * max(len(p), 1)).from_buffer_copy(p or b"\0") for p, _, _ in self.rules]
+        self._arr = (SrRule * max(len(self.rules), 1))()
+        for i, ((p, k, a), buf) in enumerate(zip(self.rules, self._keep)):
+            self._arr[i] = SrRule(ctypes.addressof(buf), len(p), k, a)
+        self.cfg = SrRulesConfig(self._arr, len(self.rules), self.default_action)
+
+    def __len__(self):
+        return len(self.rules)
+
+    def ref(self):
+        return ctypes.byref(self.cfg)
+
+    def check(self) -> int:
+        """sr_rules_check: 0 or a negative errno."""
+        return int(lib().sr_rules_check(self.ref()))
+
+    def match(self, line: bytes) -> int:
+        """sr_rules_match: the winning rule's index for one line, len(self) for the default."""
+        buf = (ctypes.c_uint8 * max(len(line), 1)).from_buffer_copy(line or b"\0")
+        return _check(lib().sr_rules_match(self.ref(), buf, len(line)), "sr_rules_match")
+
+
+def rules_parse_text(text: bytes) -> RuleSet:
+    """sr_rules_parse_text: the rule file's text into a RuleSet. A bad file raises SrError with `.line` set to the
+    1-based line at fault."""
+    out, line = ctypes.POINTER(SrRulesConfig)(), ctypes.c_size_t(0)
+    rc = lib().sr_rules_parse_text(text, len(text), ctypes.byref(out), ctypes.byref(line))
+    if rc < 0:
+        e = SrError(-rc, f"sr_rules_parse_text: line {line.value}: {os.strerror(-rc)}")
+        e.line = int(line.value)
+        raise e
+    try:
+        cfg = out.contents
+        rules = [(ctypes.string_at(cfg.rules[i].pattern, cfg.rules[i].len), cfg.rules[i].kind, cfg.rules[i].action)
+                 for i in range(cfg.n_rules)]
+        return RuleSet(rules, cfg.default_action)
+    finally:
+        lib().sr_rules_free(out)
 
 
 class SrStatsSnapshot(ctypes.Structure):
@@ -491,6 +571,18 @@ def _load_route_lib() -> ctypes.CDLL:
         "sr_coalesce_format": (ctypes.c_size_t, [vp, vp, ctypes.c_uint32, ctypes.c_int64]),
         "sr_set_coalesce": (ctypes.c_int, [vp, ctypes.POINTER(SrCoalesceConfig)]),
         "sr_route_pack_coalesced": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(vp), c_size_p, u64p]),
+        "sr_rules_open": (ctypes.c_int, [vp, ctypes.POINTER(SrRulesConfig)]),
+        "sr_rules_close": (ctypes.c_int, [vp]),
+        "sr_rules": (ctypes.c_int, [vp, ctypes.POINTER(SrRulesBatch), ctypes.c_size_t]),
+        "sr_rules_read": (ctypes.c_int, [vp, ctypes.POINTER(SrRuleHits), ctypes.c_size_t]),
+        "sr_rules_reset": (ctypes.c_int, [vp]),
+        "sr_rules_check": (ctypes.c_int, [ctypes.POINTER(SrRulesConfig)]),
+        "sr_rules_match": (ctypes.c_int, [ctypes.POINTER(SrRulesConfig), vp, ctypes.c_size_t]),
+        "sr_rules_parse_text": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t,
+                                               ctypes.POINTER(ctypes.POINTER(SrRulesConfig)), c_size_p]),
+        "sr_rules_free": (None, [ctypes.POINTER(SrRulesConfig)]),
+        "sr_set_name_rules": (ctypes.c_int, [vp, ctypes.POINTER(SrRulesConfig)]),
+        "sr_route_pack_rules": (ctypes.c_int, [vp, ctypes.c_int, u64p]),
     }
     for name in ABI_FUNCTIONS:
         if os.environ.get("SR_ROUTE_LIB") and not hasattr(lib, name):
@@ -952,6 +1044,52 @@ class Router:
                "sr_route_pack_coalesced")
         raw = bytes((ctypes.c_uint8 * n.value).from_address(text.value)) if n.value else b""
         return raw, np.array(list(counts), np.uint64)
+
+    def rules_open(self, rules: RuleSet) -> None:
+        """sr_rules_open: the name rules' stage of this context, with the compiled set uploaded."""
+        _check(self._lib.sr_rules_open(self._h, rules.ref()), "sr_rules_open")
+        self._n_rules = len(rules)
+
+    def rules_close(self) -> None:
+        _check(self._lib.sr_rules_close(self._h), "sr_rules_close")
+
+    @staticmethod
+    def rules_batches(batches):
+        """The sr_rules_batch array of [(d_bytes, nbytes, d_recs, d_n_records, max_records, d_out, d_hashes,
+        d_hashes_out, d_match, d_counts), ...] (raw device addresses; 0 = NULL)."""
+        arr = (SrRulesBatch * max(len(batches), 1))()
+        for i, (db, nb, dr, dn, mr, do, dh, dho, dm, dc) in enumerate(batches):
+            arr[i] = SrRulesBatch(db or None, nb, dr or None, dn or None, mr, do or None, dh or None, dho or None,
+                                  dm or None, dc or None)
+        return arr
+
+    def rules(self, batches) -> None:
+        """sr_rules over the batches of one route launch (as rules_batches takes them, or its array), asynchronous
+        on the context's stream."""
+        arr = batches if isinstance(batches, ctypes.Array) else self.rules_batches(batches)
+        _check(self._lib.sr_rules(self._h, arr, len(batches)), "sr_rules")
+
+    def rules_read(self, n: int | None = None) -> np.ndarray:
+        """sr_rules_read: the hits as an array of [lines, bytes] rows, one per rule and the default's last."""
+        n = SR_RULES_MAX + 1 if n is None else n
+        hits = (SrRuleHits * max(n, 1))()
+        m = _check(self._lib.sr_rules_read(self._h, hits, n), "sr_rules_read")
+        return np.array([[hits[i].lines, hits[i].bytes] for i in range(m)], np.uint64).reshape(m, 2)
+
+    def rules_reset(self) -> None:
+        _check(self._lib.sr_rules_reset(self._h), "sr_rules_reset")
+
+    def set_name_rules(self, rules: RuleSet | None) -> None:
+        """sr_set_name_rules: later route_pack submissions drop the lines that the set drops, between the route and
+        the packing (None: off)."""
+        _check(self._lib.sr_set_name_rules(self._h, rules.ref() if rules is not None else None), "sr_set_name_rules")
+
+    def route_pack_rules(self, slot: int) -> np.ndarray:
+        """sr_route_pack_rules after route_pack_result(slot) (route_pack: slot 2): [out, dropped, bytes dropped,
+        subject]."""
+        counts = (ctypes.c_uint64 * 4)()
+        _check(self._lib.sr_route_pack_rules(self._h, slot, counts), "sr_route_pack_rules")
+        return np.array(list(counts), np.uint64)
 
     def route_pack_submit_slots(self, slot: int, slots, stride: int, lens, fill=None) -> None:
         """sr_route_pack_submit_slots (asynchronous): `slots` is page-locked memory (a HostBuffer, or its

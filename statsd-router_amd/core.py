@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from . import LIB_DIR, SrCoalesceConfig, SrError, SrStatsConfig, SrStatsSnapshot, StatsSnapshot, _check, alive_words, lib
+from . import LIB_DIR, SR_RULES_MAX, SrCoalesceConfig, SrError, SrRuleHits, SrRulesConfig, SrStatsConfig, SrStatsSnapshot, StatsSnapshot, _check, alive_words, lib
 
 ROUTER_LIB = os.path.join(LIB_DIR, "libsr_router.so")
 SR_TRACE, SR_DEBUG, SR_INFO, SR_WARN, SR_ERROR = range(5)
@@ -84,6 +84,10 @@ def router_lib() -> ctypes.CDLL:
         L.sr_core_set_coalesce.argtypes = [vp, ctypes.POINTER(SrCoalesceConfig)]
         L.sr_core_coalesce_counts.restype = ctypes.c_int
         L.sr_core_coalesce_counts.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
+        L.sr_core_set_name_rules.restype = ctypes.c_int
+        L.sr_core_set_name_rules.argtypes = [vp, ctypes.POINTER(SrRulesConfig)]
+        L.sr_core_name_rule_hits.restype = ctypes.c_int
+        L.sr_core_name_rule_hits.argtypes = [vp, ctypes.POINTER(SrRuleHits), ctypes.c_size_t, ctypes.c_int]
         L.sr_core_device_log_stats.restype = ctypes.c_int
         L.sr_core_device_log_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         _RLIB = L
@@ -245,6 +249,18 @@ class Core:
         """sr_core_set_coalesce: later batches have their plain counters coalesced on the GPU."""
         _check(self._L.sr_core_set_coalesce(self._h, ctypes.byref(SrCoalesceConfig(slots)) if on else None),
                "sr_core_set_coalesce")
+
+    def set_name_rules(self, rules) -> None:
+        """sr_core_set_name_rules: later batches lose the lines that the RuleSet drops (None: off)."""
+        _check(self._L.sr_core_set_name_rules(self._h, rules.ref() if rules is not None else None),
+               "sr_core_set_name_rules")
+
+    def name_rule_hits(self, reset: bool = False) -> np.ndarray:
+        """sr_core_name_rule_hits: drains, then [lines, bytes] per rule and, last, for the default."""
+        hits = (SrRuleHits * (SR_RULES_MAX + 1))()
+        m = _check(self._L.sr_core_name_rule_hits(self._h, hits, SR_RULES_MAX + 1, 1 if reset else 0),
+                   "sr_core_name_rule_hits")
+        return np.array([[hits[i].lines, hits[i].bytes] for i in range(m)], np.uint64).reshape(m, 2)
 
     def coalesce_counts(self, reset: bool = False):
         """sr_core_coalesce_counts: [lines out, lines dropped, groups merged, merged text bytes] so far."""

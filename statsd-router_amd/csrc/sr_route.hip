@@ -27,6 +27,7 @@
 #include "payload_kernel.hpp"
 #include "regroup_kernel.hpp"
 #include "route_host.hpp"
+#include "rules_kernel.hpp"
 #include "stats_kernel.hpp"
 
 using namespace srk;
@@ -87,6 +88,13 @@ struct sr_ctx {
     int coalesce_on;              // sr_set_coalesce: submissions coalesce between the route and the packing
     sr_record *d_cout;            // ... into these records (one per byte of the largest batch) ...
     uint64_t *d_ccounts;          // ... and these four counts
+    RulesState rules;             // sr_rules_open: the name rules' table, hits and scratch
+    int rules_on;                 // sr_set_name_rules: submissions run the rules between the route and the packing
+    sr_record *d_rout;            // ... into these records (one per byte of the largest batch) ...
+    size_t d_rout_cap;
+    uint64_t *d_rhash;            // ... these hashes, when the coalescing follows ...
+    size_t d_rhash_cap;
+    uint64_t *d_rcounts;          // ... and these four counts
     // packing knobs (sr_set_knob): forced chunk lines (0: by shape), XCD-local chunks, chain walked in emit
     uint32_t mtu_chunk;
     int mtu_xcd, mtu_walk;
@@ -119,6 +127,9 @@ struct sr_ctx {
         uint8_t *chost, *cdev;
         size_t ctext_cap;
         int coalesced;            // the batch in the slot was submitted with the coalescing on
+        // sr_set_name_rules: {4 counts, input records} (one more page-locked allocation)
+        uint64_t *rhost, *rdev;
+        int ruled;                // the batch in the slot was submitted with the name rules on
         // sr_set_logtext: text | offsets | levels | {total, messages} | staged prefixes | staged ends
         uint8_t *lhost, *ldev;
         size_t ltext_cap, lmsg_cap;
@@ -251,12 +262,20 @@ void sr_close(sr_ctx *c) {
     free_ptr(c->coalesce.d_tiles);
     free_ptr(c->d_cout);
     free_ptr(c->d_ccounts);
+    free_ptr(c->rules.d_table);
+    free_ptr(c->rules.d_hits);
+    free_ptr(c->rules.d_match);
+    free_ptr(c->rules.d_tiles);
+    free_ptr(c->d_rout);
+    free_ptr(c->d_rhash);
+    free_ptr(c->d_rcounts);
     for (auto &sl : c->slot) {
         if (sl.host) (void)hipHostFree(sl.host);
         if (sl.thost) (void)hipHostFree(sl.thost);
         if (sl.phost) (void)hipHostFree(sl.phost);
         if (sl.lhost) (void)hipHostFree(sl.lhost);
         if (sl.chost) (void)hipHostFree(sl.chost);
+        if (sl.rhost) (void)hipHostFree(sl.rhost);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1348,6 +1367,191 @@ size_t sr_coalesce_format(uint8_t *dst, const uint8_t *name, uint32_t name_len, 
     return coalesce_format_line(dst, name, name_len, sum);
 }
 
+// ---- name rules (rules_kernel.hpp, rules_host.hpp) ----------------------------------------------------------
+int sr_rules_open(sr_ctx *c, const sr_rules_config *cfg) {
+    if (!c) return -EINVAL;
+    RulesState &st = c->rules;
+    if (st.open) return -EBUSY;
+    (void)hipSetDevice(c->device);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;   // it allocates and waits: not inside a capture
+    if (hipStreamIsCapturing(c->stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return -EINVAL;
+    RulesTable *t = (RulesTable *)malloc(sizeof(RulesTable));
+    if (!t) return -ENOMEM;
+    if (rules_compile(cfg, t) != 0) {
+        free(t);
+        return -EINVAL;
+    }
+    (void)hipSetDevice(c->device);
+    int rc = 0;
+    if (hipMalloc(&st.d_table, sizeof(RulesTable)) != hipSuccess) {
+        st.d_table = nullptr;
+        rc = -ENOMEM;
+    } else if (hipMalloc(&st.d_hits, kRulesHitCells * sizeof(unsigned long long)) != hipSuccess) {
+        st.d_hits = nullptr;
+        rc = -ENOMEM;
+    } else if (hipMemcpyAsync(st.d_table, t, sizeof(RulesTable), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+               hipMemsetAsync(st.d_hits, 0, kRulesHitCells * sizeof(unsigned long long), c->stream) != hipSuccess ||
+               hipStreamSynchronize(c->stream) != hipSuccess) {   // t is pageable: the copy is done before it is freed
+        rc = -EIO;
+    }
+    const uint32_t n_rules = t->n_rules;
+    free(t);
+    if (rc) {
+        (void)hipGetLastError();
+        free_ptr(st.d_table);
+        free_ptr(st.d_hits);
+        memset(&st, 0, sizeof(st));
+        return rc;
+    }
+    st.n_rules = n_rules;
+    st.open = 1;
+    return 0;
+}
+
+int sr_rules_close(sr_ctx *c) {
+    if (!c) return -EINVAL;
+    RulesState &st = c->rules;
+    for (int k = 0; k < 3; ++k)
+        if (c->slot[k].busy) return -EBUSY;
+    if (!st.open) return 0;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    free_ptr(st.d_table);
+    free_ptr(st.d_hits);
+    free_ptr(st.d_match);
+    free_ptr(st.d_tiles);
+    memset(&st, 0, sizeof(st));
+    c->rules_on = 0;
+    return 0;
+}
+
+int sr_rules(sr_ctx *c, const sr_rules_batch *batches, size_t count) {
+    static_assert(kRulesMaxBatches == (int)SR_MAX_BATCHES_PER_LAUNCH, "launch batch limit");
+    if (!c || !c->rules.open || !batches || count == 0 || count > (size_t)kRulesMaxBatches) return -EINVAL;
+    RulesState &st = c->rules;
+    size_t records = 0, tiles = 0;   // the scratch's sizes, by max_records
+    uint64_t grid_tiles = 0;         // the grid's bound only (the kernels number the tiles by the device's counts)
+    for (size_t j = 0; j < count; ++j) {
+        const sr_rules_batch &b = batches[j];
+        if (!b.d_n_records || !b.d_counts || (b.nbytes && !b.d_bytes)) return -EINVAL;
+        if (b.max_records && (!b.d_recs || !b.d_out || b.d_out == b.d_recs)) return -EINVAL;
+        if (b.d_hashes && b.d_hashes_out == b.d_hashes) return -EINVAL;
+        if ((const void *)b.d_counts == (const void *)b.d_n_records) return -EINVAL;   // read after the counts are written
+        if (b.nbytes > 0xFFFFFFF0ull || b.max_records > 0xFFFFFFF0ull) return -EINVAL;
+        if (!b.d_match) records += b.max_records;
+        tiles += (b.max_records + kRulesTile - 1) / kRulesTile;
+        const uint64_t likely = (uint64_t)b.nbytes / kRulesGridLineBytes + 1u;
+        const uint64_t room = b.max_records < likely ? b.max_records : likely;
+        grid_tiles += (room + kRulesTile - 1) / kRulesTile;
+    }
+    (void)hipSetDevice(c->device);
+    int rc;
+    if ((rc = grow((void **)&st.d_match, &st.match_cap, records, sizeof(uint16_t)))) return rc;
+    if ((rc = grow((void **)&st.d_tiles, &st.tiles_cap, tiles, sizeof(uint4)))) return rc;
+    RulesArgs a;
+    memset(&a, 0, sizeof(a));
+    size_t at = 0;
+    for (size_t j = 0; j < count; ++j) {
+        const sr_rules_batch &b = batches[j];
+        RulesBatchArg &o = a.b[j];
+        const bool hashes = b.d_hashes && b.d_hashes_out;
+        o.bytes = b.d_bytes;
+        o.recs = b.d_recs;
+        o.n_records = b.d_n_records;
+        o.hashes = hashes ? b.d_hashes : nullptr;
+        o.out = b.d_out;
+        o.hashes_out = hashes ? b.d_hashes_out : nullptr;
+        o.match = b.d_match ? b.d_match : st.d_match + at;
+        o.counts = b.d_counts;
+        o.nbytes = (uint32_t)b.nbytes;
+        o.max_records = (uint32_t)b.max_records;
+        if (!b.d_match) at += b.max_records;
+    }
+    a.table = st.d_table;
+    a.hits = st.d_hits;
+    a.tiles = st.d_tiles;
+    a.nb = (uint32_t)count;
+    a.nds = c->ds.nds;
+    if (grid_tiles) {
+        const dim3 grid((uint32_t)(grid_tiles < (uint64_t)kRulesGroups ? grid_tiles : (uint64_t)kRulesGroups));
+        hipLaunchKernelGGL(rules_match_kernel, grid, dim3(kRulesBlock), 0, c->stream, a);
+        hipLaunchKernelGGL(rules_scan_kernel, dim3((uint32_t)count), dim3(kRulesScanBlock), 0, c->stream, a);
+        hipLaunchKernelGGL(rules_emit_kernel, grid, dim3(kRulesBlock), 0, c->stream, a);
+    } else {   // no batch has room for a record: the counts alone
+        hipLaunchKernelGGL(rules_scan_kernel, dim3((uint32_t)count), dim3(kRulesScanBlock), 0, c->stream, a);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+int sr_rules_read(sr_ctx *c, sr_rule_hits *hits, size_t n) {
+    static_assert(sizeof(sr_rule_hits) == 2 * sizeof(unsigned long long), "a hit is two cells");
+    if (!c || !c->rules.open || (n && !hits)) return -EINVAL;
+    const size_t m = n < (size_t)c->rules.n_rules + 1 ? n : (size_t)c->rules.n_rules + 1;
+    (void)hipSetDevice(c->device);
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return -EIO;
+    if (m && hipMemcpy(hits, c->rules.d_hits, m * sizeof(sr_rule_hits), hipMemcpyDeviceToHost) != hipSuccess) return -EIO;
+    return (int)m;
+}
+
+int sr_rules_reset(sr_ctx *c) {
+    if (!c || !c->rules.open) return -EINVAL;
+    (void)hipSetDevice(c->device);
+    return hipMemsetAsync(c->rules.d_hits, 0, kRulesHitCells * sizeof(unsigned long long), c->stream) == hipSuccess ? 0 : -EIO;
+}
+
+int sr_rules_check(const sr_rules_config *cfg) {
+    RulesTable *t = (RulesTable *)malloc(sizeof(RulesTable));
+    if (!t) return -ENOMEM;
+    const int rc = rules_compile(cfg, t);
+    free(t);
+    return rc;
+}
+
+int sr_rules_match(const sr_rules_config *cfg, const uint8_t *line, size_t len) {
+    if (len && !line) return -EINVAL;
+    RulesTable *t = (RulesTable *)malloc(sizeof(RulesTable));
+    if (!t) return -ENOMEM;
+    int rc = rules_compile(cfg, t);
+    if (rc == 0) rc = (int)rules_match(*t, line, len);
+    free(t);
+    return rc;
+}
+
+int sr_rules_parse_text(const char *text, size_t len, sr_rules_config **out, size_t *err_line) {
+    return rules_parse_text(text, len, out, err_line);
+}
+
+void sr_rules_free(sr_rules_config *cfg) { free(cfg); }
+
+int sr_set_name_rules(sr_ctx *c, const sr_rules_config *cfg) {
+    if (!c) return -EINVAL;
+    for (int k = 0; k < 3; ++k)
+        if (c->slot[k].busy) return -EBUSY;
+    if (!cfg) {
+        c->rules_on = 0;
+        return 0;
+    }
+    int rc = sr_rules_check(cfg);   // a bad set leaves the stage as it was
+    if (rc) return rc;
+    if (c->rules.open && (rc = sr_rules_close(c))) return rc;
+    if ((rc = sr_rules_open(c, cfg))) return rc;
+    (void)hipSetDevice(c->device);
+    if (!c->d_rcounts && hipMalloc(&c->d_rcounts, 4 * sizeof(uint64_t)) != hipSuccess) {
+        c->d_rcounts = nullptr;
+        return -ENOMEM;
+    }
+    c->rules_on = 1;
+    return 0;
+}
+
+int sr_route_pack_rules(sr_ctx *c, int slot, uint64_t counts[4]) {
+    if (!c || !counts || slot < 0 || slot > 2) return -EINVAL;
+    const sr_ctx::Slot &sl = c->slot[slot];
+    if (sl.busy || !sl.ruled || !sl.rhost) return -EBUSY;
+    for (int q = 0; q < 4; ++q) counts[q] = sl.rhost[q];
+    return 0;
+}
+
 // Host outputs of a slot for batches of up to nbytes (grown, never shrunk; the slot is idle).
 static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static int slot_reserve(sr_ctx *c, int k, size_t nbytes) {
@@ -1450,6 +1654,21 @@ static int slot_coalesce_reserve(sr_ctx *c, int k, size_t nbytes) {
     return 0;
 }
 
+// sr_set_name_rules: the slot's counts (the slot is idle): 4 counts and the input's record count
+static int slot_rules_reserve(sr_ctx *c, int k) {
+    sr_ctx::Slot &sl = c->slot[k];
+    if (sl.rhost) return 0;
+    void *h = nullptr, *d = nullptr;
+    if (hipHostMalloc(&h, 64, hipHostMallocMapped) != hipSuccess) return -ENOMEM;
+    if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
+        (void)hipHostFree(h);
+        return -EIO;
+    }
+    sl.rhost = (uint64_t *)h;
+    sl.rdev = (uint64_t *)d;
+    return 0;
+}
+
 // sr_set_logtext: the slot's text arena, index, totals and the staging of prefixes and ends (sized by the
 // switch, which only changes while every slot is idle)
 struct LogLayout {
@@ -1520,6 +1739,8 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
     if (c->logtext && (rc = slot_log_reserve(c, k))) return rc;
     const bool coalesce = c->coalesce_on != 0;
     if (coalesce && (rc = slot_coalesce_reserve(c, k, full))) return rc;
+    const bool rules = c->rules_on != 0;
+    if (rules && (rc = slot_rules_reserve(c, k))) return rc;
     const bool log_trace = c->logtext && c->log_level == 0;   // the formatter needs hashes and datagram ends
     if (log_trace && src && !c->d_ends && hipMalloc(&c->d_ends, (size_t)SR_MAX_SLOTS * sizeof(uint32_t)) != hipSuccess) {
         c->d_ends = nullptr;
@@ -1570,7 +1791,28 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
             hashes = c->d_hash;
         }
         const sr_batch rb{c->d_in, nbytes, c->d_out, cap, hashes, c->d_count, c->d_probed};
-        if (!coalesce) {
+        if (rules) {   // route, rules, coalesce when on, pack: each stage reads the one before's records and count
+            if ((rc = grow((void **)&c->d_rout, &c->d_rout_cap, full, sizeof(sr_record)))) return rc;
+            if (coalesce && (rc = grow((void **)&c->d_rhash, &c->d_rhash_cap, full, sizeof(uint64_t)))) return rc;
+            if (coalesce && !c->d_cout && hipMalloc(&c->d_cout, full * sizeof(sr_record)) != hipSuccess) {
+                c->d_cout = nullptr;
+                return -ENOMEM;
+            }
+            RouteParams p = c->ds.params();
+            DeviceState::add_batch(p, rb.d_bytes, rb.nbytes, rb.d_out, rb.max_records, rb.d_hashes, rb.d_n_records,
+                                   rb.d_probed_dead);
+            if ((rc = launch_variant(c->ds, p, c->stream))) return rc;
+            const sr_rules_batch ub{c->d_in, nbytes, c->d_out, c->d_count, cap, c->d_rout, coalesce ? c->d_hash : nullptr,
+                                    coalesce ? c->d_rhash : nullptr, nullptr, c->d_rcounts};
+            if ((rc = sr_rules(c, &ub, 1))) return rc;
+            if (coalesce) {
+                const sr_coalesce_batch cb{c->d_in, nbytes, nbytes, c->d_rout, c->d_rcounts, cap, c->d_rhash, c->d_cout, c->d_ccounts};
+                if ((rc = sr_coalesce(c, &cb, 1))) return rc;
+            }
+            const sr_pack_batch pb{coalesce ? c->d_cout : c->d_rout, coalesce ? c->d_ccounts : c->d_rcounts, cap, f_in,
+                                   c->d_probed, c->d_sorted, c->d_packets, pcap, c->d_mcounts, f_out};
+            if ((rc = pack_many_impl(c, &pb, 1, nullptr, nullptr))) return rc;
+        } else if (!coalesce) {
             const sr_pack_batch pb{c->d_out, c->d_count, cap, f_in, c->d_probed, c->d_sorted, c->d_packets, pcap,
                                    c->d_mcounts, f_out};
             if ((rc = route_pack_impl(c, &rb, &pb, 1))) return rc;
@@ -1611,8 +1853,9 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
     sl.traced = c->trace;
     // input order, and the hashes (sr_route_pack_trace); with the coalescing on coalesce_out_kernel copies them,
     // by the input's count
-    o.recs = (c->trace && nbytes && !coalesce) ? c->d_out : nullptr;
-    o.hashes = (c->trace && nbytes && !coalesce) ? c->d_hash : nullptr;
+    // (with the name rules on rules_out_kernel does, unless the coalescing is on too)
+    o.recs = (c->trace && nbytes && !coalesce && !rules) ? c->d_out : nullptr;
+    o.hashes = (c->trace && nbytes && !coalesce && !rules) ? c->d_hash : nullptr;
     o.h_recs = c->trace ? (sr_record *)sl.tdev : nullptr;
     o.h_hashes = c->trace ? (uint64_t *)(sl.tdev + up256(sl.trec_cap * sizeof(sr_record))) : nullptr;
     // one workgroup per 512 records (two per thread), at most 1024 workgroups (grid-stride beyond)
@@ -1640,6 +1883,26 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
             co.h_hashes = c->trace ? (uint64_t *)(sl.tdev + up256(sl.trec_cap * sizeof(sr_record))) : nullptr;
             hipLaunchKernelGGL(coalesce_out_kernel, dim3((uint32_t)(want < 1024 ? (want ? want : 1) : 1024)),
                                dim3(kCoalesceBlock), 0, c->stream, co);
+            if (hipGetLastError() != hipSuccess) return -EIO;
+        }
+    }
+    sl.ruled = rules;
+    if (rules) {   // the stage's counts and the input's record count into the slot's page-locked memory
+        if (nbytes == 0) {
+            for (int q = 0; q < 5; ++q) sl.rhost[q] = 0;   // the slot is idle: nothing is in flight that writes here
+        } else {
+            const bool tr = c->trace && !coalesce;
+            RulesOut ro;
+            ro.counts = c->d_rcounts;
+            ro.n_records = c->d_count;
+            ro.rec_cap = tr ? sl.trec_cap : 0;
+            ro.h_counts = sl.rdev;
+            ro.recs = tr ? c->d_out : nullptr;
+            ro.hashes = tr ? c->d_hash : nullptr;
+            ro.h_recs = tr ? (sr_record *)sl.tdev : nullptr;
+            ro.h_hashes = tr ? (uint64_t *)(sl.tdev + up256(sl.trec_cap * sizeof(sr_record))) : nullptr;
+            hipLaunchKernelGGL(rules_out_kernel, dim3((uint32_t)(!tr ? 1 : want < 1024 ? (want ? want : 1) : 1024)),
+                               dim3(kRulesBlock), 0, c->stream, ro);
             if (hipGetLastError() != hipSuccess) return -EIO;
         }
     }
@@ -1707,7 +1970,10 @@ int sr_route_pack_trace(sr_ctx *c, int slot, const sr_record **records, const ui
     const sr_ctx::Slot &sl = c->slot[slot];
     if (sl.busy || !sl.traced || !sl.thost || !sl.counts) return -EBUSY;
     // the input's records: with the coalescing on counts[2] is the coalesced batch's
-    const uint64_t nr = (sl.coalesced && sl.chost) ? ((const uint64_t *)(sl.chost + up256(sl.ctext_cap)))[4] : sl.counts[2];
+    // (and with the name rules on the kept lines')
+    const uint64_t nr = (sl.coalesced && sl.chost) ? ((const uint64_t *)(sl.chost + up256(sl.ctext_cap)))[4]
+                        : (sl.ruled && sl.rhost)   ? sl.rhost[4]
+                                                   : sl.counts[2];
     *n = (size_t)(nr < sl.trec_cap ? nr : sl.trec_cap);
     *records = (const sr_record *)sl.thost;
     *hashes = (const uint64_t *)(sl.thost + up256(sl.trec_cap * sizeof(sr_record)));
