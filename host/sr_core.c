@@ -686,6 +686,29 @@ int sr_core_name_rule_hits(sr_core *c, sr_rule_hits *hits, size_t n, int reset) 
     return got;
 }
 
+int sr_core_set_validate(sr_core *c, const sr_validate_config *cfg) {
+    if (!c) return -EINVAL;
+    if (c->in_flight >= 0) return -EBUSY;
+    int rc = sr_set_validate(c->ctx, cfg);
+    if (rc) return rc;
+    /* both slots' counts allocated now (an empty batch each; the device's pending bytes carry over) */
+    for (int k = 0; cfg && k < 2; k++) {
+        sr_pack_result r;
+        if ((rc = sr_route_pack_submit(c->ctx, k, NULL, 0, NULL)) || (rc = sr_route_pack_result(c->ctx, k, &r))) return rc;
+    }
+    return 0;
+}
+
+int sr_core_validate_hits(sr_core *c, sr_validate_hits *hits, size_t n, int reset) {
+    if (!c || (n && !hits)) return -EINVAL;
+    int rc = sr_core_drain(c);
+    if (rc) return rc;
+    const int got = sr_validate_read(c->ctx, hits, n);
+    if (got < 0) return got;
+    if (reset && (rc = sr_validate_reset(c->ctx))) return rc;
+    return got;
+}
+
 int sr_core_coalesce_counts(sr_core *c, uint64_t totals[4], int reset) {
     if (!c || !totals) return -EINVAL;
     memcpy(totals, c->co_totals, sizeof(c->co_totals));

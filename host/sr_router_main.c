@@ -328,6 +328,31 @@ static void log_name_rules(data_thread *d) {
            text[0] ? text : " none");
 }
 
+/* SR_VALIDATE=<spec>: what the grammar dropped since the thread's last ping and the lines per reason (the non-zero
+ * ones, in index order), then the hits start again. */
+static void log_validate(data_thread *d) {
+    const sr_validate_config *cfg = d->c->dt_validate;
+    sr_validate_hits hits[SR_VALID_REASONS];
+    const int n = sr_core_validate_hits(d->core, hits, SR_VALID_REASONS, 1);
+    if (n < 0) {
+        sr_log(SR_ERROR, "%s: sr_core_validate_hits() failed %s", "ping_cb", strerror(-n));
+        return;
+    }
+    uint64_t lines = 0, bytes = 0;
+    char text[SR_VALID_REASONS * 40] = "";
+    size_t used = 0;
+    for (int i = 0; i < n; i++) {
+        if ((cfg->drop_mask >> i) & 1u) {
+            lines += hits[i].lines;
+            bytes += hits[i].bytes;
+        }
+        if (!hits[i].lines || used >= sizeof(text)) continue;
+        used += (size_t)snprintf(text + used, sizeof(text) - used, " %s=%llu", sr_validate_reason_name((uint32_t)i),
+                                 (unsigned long long)hits[i].lines);
+    }
+    sr_log(SR_INFO, "validate: dropped lines=%llu bytes=%llu%s", (unsigned long long)lines, (unsigned long long)bytes, text);
+}
+
 /* SR_NAME_STATS=1: what the thread routed since its last ping, then the statistics start again. A thread that
  * routed no valid line logs nothing. */
 #define NAME_STATS_HOT_LINES 8
@@ -365,6 +390,7 @@ static void ping_timer_cb(struct ev_loop *loop, ev_periodic *p, int revents) {
     if (rc) sr_log(SR_ERROR, "%s: sr_core_ping() failed %s", "ping_cb", strerror(-rc));
     if (d->c->dt_name_stats) log_name_stats(d);
     if (d->c->dt_name_rules) log_name_rules(d);
+    if (d->c->dt_validate) log_validate(d);
 }
 
 /* a data thread that cannot route: the process ends (status 1) unless SR_REQUIRE_GPU=0 */
@@ -437,6 +463,10 @@ void *sr_data_thread(void *arg) {
             sr_log(SR_ERROR, "%s: sr_core_set_name_stats() failed %s", fn, strerror(-rc));
             return thread_fail(d, 1);
         }
+    }
+    if (c->dt_validate && (rc = sr_core_set_validate(d->core, c->dt_validate))) {
+        sr_log(SR_ERROR, "%s: sr_core_set_validate() failed %s", fn, strerror(-rc));
+        return thread_fail(d, 1);
     }
     if (c->dt_name_rules && (rc = sr_core_set_name_rules(d->core, c->dt_name_rules))) {
         sr_log(SR_ERROR, "%s: sr_core_set_name_rules() failed %s", fn, strerror(-rc));
@@ -573,6 +603,16 @@ int main(int argc, char *argv[]) {
         sr_log(SR_INFO, "%s: name_rules: %u rules, default %s", "main", rules->n_rules,
                rules->default_action == SR_RULE_DROP ? "drop" : "keep");
         config.dt_name_rules = rules;   /* lives as long as the process */
+    }
+    const char *vs = getenv("SR_VALIDATE");
+    if (vs && vs[0]) {   /* a bad spec is a config error */
+        static sr_validate_config validate;   /* lives as long as the process */
+        if (sr_validate_parse_spec(vs, &validate) != 0) {
+            sr_log(SR_ERROR, "%s: SR_VALIDATE %s: not count, drop or a comma list of reason names", "main", vs);
+            exit(1);
+        }
+        sr_log(SR_INFO, "%s: validate: %s", "main", vs);
+        config.dt_validate = &validate;
     }
     config.dt_yield = dy ? atoi(dy) : 0;
     config.dt_yield_s = dys ? atof(dys) : READ_EVENT_SECONDS;

@@ -1034,6 +1034,120 @@ void sr_rules_free(sr_rules_config *cfg);
 int sr_set_name_rules(sr_ctx *ctx, const sr_rules_config *cfg_or_null);
 int sr_route_pack_rules(sr_ctx *ctx, int slot, uint64_t counts[4]);
 
+/* ---- line grammar on the device: count or drop lines that no statsd would parse --------------------- */
+/* The router forwards any line that has a ':' and a legal length. This stage looks at what stands behind the
+ * name: it consumes the input-order records of a route launch, and the hashes when given, judges every line
+ * against the statsd line grammar below and writes a shorter record list, as sr_rules does; sr_rules, sr_coalesce
+ * and the packing run unchanged on the result. Exact and deterministic (tests/validate_expect.py restates it).
+ *
+ * Subject records: a record (o, L, r) is subject iff r < n_downstreams, L >= 1 and o + L <= nbytes (sr_rules'
+ *   rule). Every other record passes through untouched with the reason SR_VALID_NOT_SUBJECT. No byte outside
+ *   [0, nbytes) is ever read.
+ * Content: the content C of a subject record is its L bytes without the last byte when that byte is '\n'. A line
+ *   that ends its batch without a newline is judged on all L bytes.
+ * Byte classes: TB is 0x21..0x7E except '|'; NB is TB except ':'. A '\n', NUL or high byte inside C is simply
+ *   outside both classes.
+ * Judgement: the first failing step gives the reason; the steps in this order:
+ *   1. p = the index of the first ':' in C. None: NO_COLON. p == 0: EMPTY_NAME. A byte of C[0:p] outside NB:
+ *      NAME_BYTE.
+ *   2. C[p+1:] is split at every '|' into the fields f0 .. fk. k == 0: NO_TYPE.
+ *   3. f1 is one of c g ms h s d, and its bit (SR_VALID_TYPE_*) is set in accept_types; otherwise TYPE.
+ *   4. f0 against the type; anything else, the empty value included, is VALUE:
+ *        number = [0-9]{1,20}(\.[0-9]{1,20})?
+ *        c: -?number     g: [+-]?number     ms, h, d: number     s: 1 to 64 bytes of TB
+ *   5. f2 .. fk from left to right: a field begins with '@' or '#', there is at most one of each and '@' comes
+ *      before '#'; otherwise SECTION. After '@' comes number and the type is c, ms, h or d; otherwise RATE.
+ *      After '#' come 1 or more bytes of TB (':' and ',' are legal there); otherwise TAGS.
+ *   6. OK.
+ * Configuration: a subject record whose reason's bit is set in drop_mask is dropped; every other record is kept.
+ *   drop_mask == 0 counts and drops nothing. -EINVAL: bit 0 (OK) or a bit at or above SR_VALID_REASONS in
+ *   drop_mask, accept_types == 0, an unknown bit in accept_types.
+ * Output, as sr_rules: d_out receives the kept and the non-subject records in input order; when d_hashes and
+ *   d_hashes_out are both given the hashes are compacted alongside. The optional d_reason (u8 per input record)
+ *   receives the reason. d_counts: four u64 {records out, records dropped, bytes dropped, subject records};
+ *   &d_counts[0] is what the next stage takes as d_n_records. Of a batch the first
+ *   min(*d_n_records, max_records) records are read.
+ * Hits: the context keeps {lines, bytes} as u64 per reason, SR_VALID_REASONS pairs (index 0: the OK lines),
+ *   accumulated over all calls since sr_validate_open or the last sr_validate_reset.
+ *
+ * sr_validate_open, sr_validate, sr_validate_read, sr_validate_reset, sr_validate_close: as their sr_rules
+ *   namesakes — the same returns, the same alignment rules (d_reason has any alignment) and pointer checks
+ *   (d_out != d_recs, d_hashes_out != d_hashes, d_counts != d_n_records, nbytes and max_records at most
+ *   0xFFFFFFF0), scratch on the first call or a larger one, capturable afterwards, 1..SR_MAX_BATCHES_PER_LAUNCH
+ *   batches per call; sr_close closes the stage. sr_validate_read copies the first min(n, SR_VALID_REASONS) pairs.
+ *
+ * Host only (no GPU):
+ *   sr_validate_check      : 0 or -EINVAL for a configuration;
+ *   sr_validate_line       : the reason of one line of `len` bytes ('\n' included when it has one; len >= 1),
+ *     -EINVAL for a bad configuration, a null line or len == 0;
+ *   sr_validate_reason_name: ok, no_colon, empty_name, name_byte, no_type, type, value, section, rate, tags;
+ *     NULL for any other number;
+ *   sr_validate_parse_spec : `count` (drop nothing), `drop` (drop every reason but OK) or a comma list of reason
+ *     names to drop, into *cfg_out with every type accepted; anything else is -EINVAL. */
+#define SR_VALID_OK           0u
+#define SR_VALID_NO_COLON     1u
+#define SR_VALID_EMPTY_NAME   2u
+#define SR_VALID_NAME_BYTE    3u
+#define SR_VALID_NO_TYPE      4u
+#define SR_VALID_TYPE         5u
+#define SR_VALID_VALUE        6u
+#define SR_VALID_SECTION      7u
+#define SR_VALID_RATE         8u
+#define SR_VALID_TAGS         9u
+#define SR_VALID_REASONS      10u
+#define SR_VALID_NOT_SUBJECT  0xFFu
+#define SR_VALID_TYPE_C       1u
+#define SR_VALID_TYPE_G       2u
+#define SR_VALID_TYPE_MS      4u
+#define SR_VALID_TYPE_H       8u
+#define SR_VALID_TYPE_S       16u
+#define SR_VALID_TYPE_D       32u
+#define SR_VALID_TYPES_ALL    63u
+
+typedef struct sr_validate_config {
+    uint32_t drop_mask;      /* bit r: drop the lines of reason r (never bit 0) */
+    uint32_t accept_types;   /* SR_VALID_TYPE_* bits                            */
+} sr_validate_config;
+
+typedef struct sr_validate_batch {
+    const uint8_t *d_bytes; size_t nbytes;        /* the routed batch                                      */
+    const sr_record *d_recs;                      /* input-order records (sr_batch.d_out)                  */
+    const uint64_t *d_n_records; size_t max_records;
+    sr_record *d_out;                             /* max_records records; not d_recs                       */
+    const uint64_t *d_hashes;                     /* optional: max_records u64 (sr_batch.d_hashes) ...     */
+    uint64_t *d_hashes_out;                       /* ... compacted into these, when both are given         */
+    uint8_t *d_reason;                            /* optional: max_records u8, the line's reason           */
+    uint64_t *d_counts;                           /* 4 u64: out, dropped, bytes dropped, subject           */
+} sr_validate_batch;
+
+typedef struct sr_validate_hits {
+    uint64_t lines, bytes;
+} sr_validate_hits;
+
+int sr_validate_open(sr_ctx *ctx, const sr_validate_config *cfg);
+int sr_validate_close(sr_ctx *ctx);
+int sr_validate(sr_ctx *ctx, const sr_validate_batch *batches, size_t count);
+int sr_validate_read(sr_ctx *ctx, sr_validate_hits *hits, size_t n);
+int sr_validate_reset(sr_ctx *ctx);
+int sr_validate_check(const sr_validate_config *cfg);
+int sr_validate_line(const sr_validate_config *cfg, const uint8_t *line, size_t len);
+const char *sr_validate_reason_name(uint32_t reason);
+int sr_validate_parse_spec(const char *text, sr_validate_config *cfg_out);
+
+/* The line grammar of the host-memory path. With sr_set_validate(ctx, cfg) (the stage is opened with cfg; an open
+ * stage is closed first, hits included) every later sr_route_pack_submit / sr_route_pack_submit_slots /
+ * sr_route_pack_batch runs the route launch, then sr_validate, then sr_rules when sr_set_name_rules is on, then
+ * sr_coalesce when sr_set_coalesce is on, then the packing. The grammar runs first, so rule hits and merges see
+ * only kept lines. `sorted`, `packets`, `fill`, n_records and n_valid then describe the kept lines. The trace
+ * (sr_route_pack_trace), the log text and the name statistics keep the route launch's records: logs and statistics
+ * are byte-identical to the switch being off. NULL turns the switch off (the stage and its hits stay until
+ * sr_validate_close). Off by default: nothing is allocated, launched or copied.
+ * Returns 0, -EINVAL (a bad configuration), -ENOMEM, -EBUSY (a slot is in flight).
+ * sr_route_pack_validate: after sr_route_pack_result(slot) (for sr_route_pack_batch: slot 2), the batch's four
+ * counts. -EBUSY when the slot is in flight or was submitted with the switch off. */
+int sr_set_validate(sr_ctx *ctx, const sr_validate_config *cfg_or_null);
+int sr_route_pack_validate(sr_ctx *ctx, int slot, uint64_t counts[4]);
+
 /* ---- owner side of the multi-GPU regroup: received lines into packets ------------------------------ */
 /* After sr_regroup_launch / sr_regroup_run the lines of the shards a GPU owns lie in d_recv_bytes /
  * d_recv_recs: every source's chunk in source order 0, 1, ..., each chunk batch 0's lines, then batch

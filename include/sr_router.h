@@ -199,6 +199,21 @@ int sr_core_coalesce_counts(sr_core *core, uint64_t totals[4], int reset);
 int sr_core_set_name_rules(sr_core *core, const sr_rules_config *cfg_or_null);
 int sr_core_name_rule_hits(sr_core *core, sr_rule_hits *hits, size_t n, int reset);
 
+/* Line grammar. With sr_core_set_validate(core, cfg) (cfg as sr_validate_open takes it, sr_route.h) every later
+ * batch of sr_core_route*, sr_core_submit* and sr_core_submit_slots has the lines whose reason cfg->drop_mask names
+ * taken out on the GPU right after the route launch, before the name rules and the coalescing when those switches
+ * are on too (sr_set_validate); with a drop_mask of 0 the lines are only counted. The kept lines, their order per
+ * downstream, the log lines and the name statistics are those of the switch being off; packets, traffic counters
+ * and pending bytes describe the kept lines. Ping lines are not subject (sr_core_ping routes them outside the
+ * submit path). NULL turns the switch off. A new configuration starts the hits again from zero.
+ * sr_core_validate_hits: drains first, then copies the first min(n, SR_VALID_REASONS) pairs {lines, bytes} per
+ * reason (index 0: the OK lines) since the configuration was given or the last reset, and returns how many it
+ * copied; reset != 0 starts them again from zero.
+ * Return 0 (hits: the count), -EINVAL (also: hits before the switch was ever on), -EBUSY (set: a batch is in
+ * flight, drain first), -ENOMEM, -EIO. */
+int sr_core_set_validate(sr_core *core, const sr_validate_config *cfg_or_null);
+int sr_core_validate_hits(sr_core *core, sr_validate_hits *hits, size_t n, int reset);
+
 /* Test hook (fault injection; nothing calls it in the executable): the fail_submit-th call of
  * sr_core_submit* fails as a failed sr_route_pack_submit (the batch is not taken), and the
  * fail_finish-th batch to complete fails as a failed sr_route_pack_result (its packets and log lines

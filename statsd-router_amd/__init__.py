@@ -65,6 +65,8 @@ ABI_FUNCTIONS = (
     "sr_set_coalesce", "sr_route_pack_coalesced",
     "sr_rules_open", "sr_rules_close", "sr_rules", "sr_rules_read", "sr_rules_reset", "sr_rules_check", "sr_rules_match",
     "sr_rules_parse_text", "sr_rules_free", "sr_set_name_rules", "sr_route_pack_rules",
+    "sr_validate_open", "sr_validate_close", "sr_validate", "sr_validate_read", "sr_validate_reset", "sr_validate_check",
+    "sr_validate_line", "sr_validate_reason_name", "sr_validate_parse_spec", "sr_set_validate", "sr_route_pack_validate",
 )
 SR_LOG_MAX_PREFIX = 256
 SR_LOG_TRACE, SR_LOG_WARN = 0, 3   # sr_log_batch.min_level and the d_levels values
@@ -309,6 +311,66 @@ def rules_parse_text(text: bytes) -> RuleSet:
         return RuleSet(rules, cfg.default_action)
     finally:
         lib().sr_rules_free(out)
+
+
+class SrValidateConfig(ctypes.Structure):
+    """struct sr_validate_config (include/sr_route.h)."""
+    _fields_ = [("drop_mask", ctypes.c_uint32), ("accept_types", ctypes.c_uint32)]
+
+
+class SrValidateBatch(ctypes.Structure):
+    """struct sr_validate_batch (include/sr_route.h): one routed batch of sr_validate."""
+    _fields_ = [("d_bytes", ctypes.c_void_p), ("nbytes", ctypes.c_size_t), ("d_recs", ctypes.c_void_p),
+                ("d_n_records", ctypes.c_void_p), ("max_records", ctypes.c_size_t), ("d_out", ctypes.c_void_p),
+                ("d_hashes", ctypes.c_void_p), ("d_hashes_out", ctypes.c_void_p), ("d_reason", ctypes.c_void_p),
+                ("d_counts", ctypes.c_void_p)]
+
+
+class SrValidateHits(ctypes.Structure):
+    """struct sr_validate_hits (include/sr_route.h)."""
+    _fields_ = [("lines", ctypes.c_uint64), ("bytes", ctypes.c_uint64)]
+
+
+(SR_VALID_OK, SR_VALID_NO_COLON, SR_VALID_EMPTY_NAME, SR_VALID_NAME_BYTE, SR_VALID_NO_TYPE, SR_VALID_TYPE, SR_VALID_VALUE,
+ SR_VALID_SECTION, SR_VALID_RATE, SR_VALID_TAGS, SR_VALID_REASONS) = range(11)
+SR_VALID_NOT_SUBJECT = 0xFF
+SR_VALID_TYPE_C, SR_VALID_TYPE_G, SR_VALID_TYPE_MS, SR_VALID_TYPE_H, SR_VALID_TYPE_S, SR_VALID_TYPE_D = 1, 2, 4, 8, 16, 32
+SR_VALID_TYPES_ALL = 63
+SR_VALID_DROP_ALL = 0x3FE   # every reason but OK
+VALIDATE_TILE = 256   # kValidTile (csrc/validate_kernel.hpp): records per tile of the grammar kernels
+
+
+class ValidateConfig:
+    """A sr_validate_config: the reasons to drop (bit r of drop_mask) and the accepted types."""
+
+    def __init__(self, drop_mask: int = 0, accept_types: int = SR_VALID_TYPES_ALL):
+        self.drop_mask, self.accept_types = int(drop_mask), int(accept_types)
+        self.cfg = SrValidateConfig(self.drop_mask, self.accept_types)
+
+    def ref(self):
+        return ctypes.byref(self.cfg)
+
+    def check(self) -> int:
+        """sr_validate_check: 0 or a negative errno."""
+        return int(lib().sr_validate_check(self.ref()))
+
+    def line(self, line: bytes) -> int:
+        """sr_validate_line: the reason of one line ('\n' included when it has one)."""
+        buf = (ctypes.c_uint8 * max(len(line), 1)).from_buffer_copy(line or b"\0")
+        return _check(lib().sr_validate_line(self.ref(), buf, len(line)), "sr_validate_line")
+
+
+def validate_reason_name(reason: int):
+    """sr_validate_reason_name: the reason's name, None for a number that is no reason."""
+    name = lib().sr_validate_reason_name(reason)
+    return name.decode() if name is not None else None
+
+
+def validate_parse_spec(text: str) -> ValidateConfig:
+    """sr_validate_parse_spec: `count`, `drop` or a comma list of reason names into a ValidateConfig."""
+    cfg = SrValidateConfig()
+    _check(lib().sr_validate_parse_spec(text.encode(), ctypes.byref(cfg)), "sr_validate_parse_spec")
+    return ValidateConfig(cfg.drop_mask, cfg.accept_types)
 
 
 class SrStatsSnapshot(ctypes.Structure):
@@ -583,6 +645,17 @@ def _load_route_lib() -> ctypes.CDLL:
         "sr_rules_free": (None, [ctypes.POINTER(SrRulesConfig)]),
         "sr_set_name_rules": (ctypes.c_int, [vp, ctypes.POINTER(SrRulesConfig)]),
         "sr_route_pack_rules": (ctypes.c_int, [vp, ctypes.c_int, u64p]),
+        "sr_validate_open": (ctypes.c_int, [vp, ctypes.POINTER(SrValidateConfig)]),
+        "sr_validate_close": (ctypes.c_int, [vp]),
+        "sr_validate": (ctypes.c_int, [vp, ctypes.POINTER(SrValidateBatch), ctypes.c_size_t]),
+        "sr_validate_read": (ctypes.c_int, [vp, ctypes.POINTER(SrValidateHits), ctypes.c_size_t]),
+        "sr_validate_reset": (ctypes.c_int, [vp]),
+        "sr_validate_check": (ctypes.c_int, [ctypes.POINTER(SrValidateConfig)]),
+        "sr_validate_line": (ctypes.c_int, [ctypes.POINTER(SrValidateConfig), vp, ctypes.c_size_t]),
+        "sr_validate_reason_name": (ctypes.c_char_p, [ctypes.c_uint32]),
+        "sr_validate_parse_spec": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(SrValidateConfig)]),
+        "sr_set_validate": (ctypes.c_int, [vp, ctypes.POINTER(SrValidateConfig)]),
+        "sr_route_pack_validate": (ctypes.c_int, [vp, ctypes.c_int, u64p]),
     }
     for name in ABI_FUNCTIONS:
         if os.environ.get("SR_ROUTE_LIB") and not hasattr(lib, name):
@@ -1089,6 +1162,51 @@ class Router:
         subject]."""
         counts = (ctypes.c_uint64 * 4)()
         _check(self._lib.sr_route_pack_rules(self._h, slot, counts), "sr_route_pack_rules")
+        return np.array(list(counts), np.uint64)
+
+    def validate_open(self, cfg: ValidateConfig) -> None:
+        """sr_validate_open: the line grammar's stage of this context."""
+        _check(self._lib.sr_validate_open(self._h, cfg.ref()), "sr_validate_open")
+
+    def validate_close(self) -> None:
+        _check(self._lib.sr_validate_close(self._h), "sr_validate_close")
+
+    @staticmethod
+    def validate_batches(batches):
+        """The sr_validate_batch array of [(d_bytes, nbytes, d_recs, d_n_records, max_records, d_out, d_hashes,
+        d_hashes_out, d_reason, d_counts), ...] (raw device addresses; 0 = NULL)."""
+        arr = (SrValidateBatch * max(len(batches), 1))()
+        for i, (db, nb, dr, dn, mr, do, dh, dho, dm, dc) in enumerate(batches):
+            arr[i] = SrValidateBatch(db or None, nb, dr or None, dn or None, mr, do or None, dh or None, dho or None,
+                                     dm or None, dc or None)
+        return arr
+
+    def validate(self, batches) -> None:
+        """sr_validate over the batches of one route launch (as validate_batches takes them, or its array),
+        asynchronous on the context's stream."""
+        arr = batches if isinstance(batches, ctypes.Array) else self.validate_batches(batches)
+        _check(self._lib.sr_validate(self._h, arr, len(batches)), "sr_validate")
+
+    def validate_read(self, n: int | None = None) -> np.ndarray:
+        """sr_validate_read: the hits as an array of [lines, bytes] rows, one per reason (row 0: the OK lines)."""
+        n = SR_VALID_REASONS if n is None else n
+        hits = (SrValidateHits * max(n, 1))()
+        m = _check(self._lib.sr_validate_read(self._h, hits, n), "sr_validate_read")
+        return np.array([[hits[i].lines, hits[i].bytes] for i in range(m)], np.uint64).reshape(m, 2)
+
+    def validate_reset(self) -> None:
+        _check(self._lib.sr_validate_reset(self._h), "sr_validate_reset")
+
+    def set_validate(self, cfg: ValidateConfig | None) -> None:
+        """sr_set_validate: later route_pack submissions drop the lines whose reason the configuration drops,
+        between the route and the name rules (None: off)."""
+        _check(self._lib.sr_set_validate(self._h, cfg.ref() if cfg is not None else None), "sr_set_validate")
+
+    def route_pack_validate(self, slot: int) -> np.ndarray:
+        """sr_route_pack_validate after route_pack_result(slot) (route_pack: slot 2): [out, dropped, bytes dropped,
+        subject]."""
+        counts = (ctypes.c_uint64 * 4)()
+        _check(self._lib.sr_route_pack_validate(self._h, slot, counts), "sr_route_pack_validate")
         return np.array(list(counts), np.uint64)
 
     def route_pack_submit_slots(self, slot: int, slots, stride: int, lens, fill=None) -> None:

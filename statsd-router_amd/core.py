@@ -10,6 +10,7 @@ import os
 
 import numpy as np
 
+from . import SR_VALID_REASONS, SrValidateConfig, SrValidateHits
 from . import LIB_DIR, SR_RULES_MAX, SrCoalesceConfig, SrError, SrRuleHits, SrRulesConfig, SrStatsConfig, SrStatsSnapshot, StatsSnapshot, _check, alive_words, lib
 
 ROUTER_LIB = os.path.join(LIB_DIR, "libsr_router.so")
@@ -88,6 +89,10 @@ def router_lib() -> ctypes.CDLL:
         L.sr_core_set_name_rules.argtypes = [vp, ctypes.POINTER(SrRulesConfig)]
         L.sr_core_name_rule_hits.restype = ctypes.c_int
         L.sr_core_name_rule_hits.argtypes = [vp, ctypes.POINTER(SrRuleHits), ctypes.c_size_t, ctypes.c_int]
+        L.sr_core_set_validate.restype = ctypes.c_int
+        L.sr_core_set_validate.argtypes = [vp, ctypes.POINTER(SrValidateConfig)]
+        L.sr_core_validate_hits.restype = ctypes.c_int
+        L.sr_core_validate_hits.argtypes = [vp, ctypes.POINTER(SrValidateHits), ctypes.c_size_t, ctypes.c_int]
         L.sr_core_device_log_stats.restype = ctypes.c_int
         L.sr_core_device_log_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         _RLIB = L
@@ -260,6 +265,17 @@ class Core:
         hits = (SrRuleHits * (SR_RULES_MAX + 1))()
         m = _check(self._L.sr_core_name_rule_hits(self._h, hits, SR_RULES_MAX + 1, 1 if reset else 0),
                    "sr_core_name_rule_hits")
+        return np.array([[hits[i].lines, hits[i].bytes] for i in range(m)], np.uint64).reshape(m, 2)
+
+    def set_validate(self, cfg) -> None:
+        """sr_core_set_validate: later batches lose the lines whose reason the ValidateConfig drops (None: off)."""
+        _check(self._L.sr_core_set_validate(self._h, cfg.ref() if cfg is not None else None), "sr_core_set_validate")
+
+    def validate_hits(self, reset: bool = False) -> np.ndarray:
+        """sr_core_validate_hits: drains, then [lines, bytes] per reason (row 0: the OK lines)."""
+        hits = (SrValidateHits * SR_VALID_REASONS)()
+        m = _check(self._L.sr_core_validate_hits(self._h, hits, SR_VALID_REASONS, 1 if reset else 0),
+                   "sr_core_validate_hits")
         return np.array([[hits[i].lines, hits[i].bytes] for i in range(m)], np.uint64).reshape(m, 2)
 
     def coalesce_counts(self, reset: bool = False):

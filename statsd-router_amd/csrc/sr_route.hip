@@ -29,6 +29,7 @@
 #include "route_host.hpp"
 #include "rules_kernel.hpp"
 #include "stats_kernel.hpp"
+#include "validate_kernel.hpp"
 
 using namespace srk;
 
@@ -95,6 +96,13 @@ struct sr_ctx {
     uint64_t *d_rhash;            // ... these hashes, when the coalescing follows ...
     size_t d_rhash_cap;
     uint64_t *d_rcounts;          // ... and these four counts
+    ValidateStage validate;       // sr_validate_open: the line grammar's configuration, hits and scratch
+    int validate_on;              // sr_set_validate: submissions run the grammar between the route and the name rules
+    sr_record *d_vout;            // ... into these records (one per byte of the largest batch) ...
+    size_t d_vout_cap;
+    uint64_t *d_vhash;            // ... these hashes, when the coalescing follows ...
+    size_t d_vhash_cap;
+    uint64_t *d_vcounts;          // ... and these four counts
     // packing knobs (sr_set_knob): forced chunk lines (0: by shape), XCD-local chunks, chain walked in emit
     uint32_t mtu_chunk;
     int mtu_xcd, mtu_walk;
@@ -130,6 +138,9 @@ struct sr_ctx {
         // sr_set_name_rules: {4 counts, input records} (one more page-locked allocation)
         uint64_t *rhost, *rdev;
         int ruled;                // the batch in the slot was submitted with the name rules on
+        // sr_set_validate: {4 counts, input records} (one more page-locked allocation)
+        uint64_t *vhost, *vdev;
+        int validated;            // the batch in the slot was submitted with the line grammar on
         // sr_set_logtext: text | offsets | levels | {total, messages} | staged prefixes | staged ends
         uint8_t *lhost, *ldev;
         size_t ltext_cap, lmsg_cap;
@@ -269,6 +280,12 @@ void sr_close(sr_ctx *c) {
     free_ptr(c->d_rout);
     free_ptr(c->d_rhash);
     free_ptr(c->d_rcounts);
+    free_ptr(c->validate.d_hits);
+    free_ptr(c->validate.d_reason);
+    free_ptr(c->validate.d_tiles);
+    free_ptr(c->d_vout);
+    free_ptr(c->d_vhash);
+    free_ptr(c->d_vcounts);
     for (auto &sl : c->slot) {
         if (sl.host) (void)hipHostFree(sl.host);
         if (sl.thost) (void)hipHostFree(sl.thost);
@@ -276,6 +293,7 @@ void sr_close(sr_ctx *c) {
         if (sl.lhost) (void)hipHostFree(sl.lhost);
         if (sl.chost) (void)hipHostFree(sl.chost);
         if (sl.rhost) (void)hipHostFree(sl.rhost);
+        if (sl.vhost) (void)hipHostFree(sl.vhost);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1552,6 +1570,164 @@ int sr_route_pack_rules(sr_ctx *c, int slot, uint64_t counts[4]) {
     return 0;
 }
 
+// ---- line grammar (validate_kernel.hpp, validate_host.hpp) --------------------------------------------------
+int sr_validate_open(sr_ctx *c, const sr_validate_config *cfg) {
+    if (!c) return -EINVAL;
+    ValidateStage &st = c->validate;
+    if (st.open) return -EBUSY;
+    (void)hipSetDevice(c->device);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;   // it allocates: not inside a capture
+    if (hipStreamIsCapturing(c->stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return -EINVAL;
+    if (validate_check(cfg) != 0) return -EINVAL;
+    int rc = 0;
+    if (hipMalloc(&st.d_hits, kValidHitCells * sizeof(unsigned long long)) != hipSuccess) {
+        st.d_hits = nullptr;
+        rc = -ENOMEM;
+    } else if (hipMemsetAsync(st.d_hits, 0, kValidHitCells * sizeof(unsigned long long), c->stream) != hipSuccess) {
+        rc = -EIO;
+    }
+    if (rc) {
+        (void)hipGetLastError();
+        free_ptr(st.d_hits);
+        memset(&st, 0, sizeof(st));
+        return rc;
+    }
+    st.cfg = *cfg;
+    st.open = 1;
+    return 0;
+}
+
+int sr_validate_close(sr_ctx *c) {
+    if (!c) return -EINVAL;
+    ValidateStage &st = c->validate;
+    for (int k = 0; k < 3; ++k)
+        if (c->slot[k].busy) return -EBUSY;
+    if (!st.open) return 0;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    free_ptr(st.d_hits);
+    free_ptr(st.d_reason);
+    free_ptr(st.d_tiles);
+    memset(&st, 0, sizeof(st));
+    c->validate_on = 0;
+    return 0;
+}
+
+int sr_validate(sr_ctx *c, const sr_validate_batch *batches, size_t count) {
+    static_assert(kValidMaxBatches == (int)SR_MAX_BATCHES_PER_LAUNCH, "launch batch limit");
+    if (!c || !c->validate.open || !batches || count == 0 || count > (size_t)kValidMaxBatches) return -EINVAL;
+    ValidateStage &st = c->validate;
+    size_t records = 0, tiles = 0;   // the scratch's sizes, by max_records
+    uint64_t grid_tiles = 0;         // the grid's bound only (the kernels number the tiles by the device's counts)
+    for (size_t j = 0; j < count; ++j) {
+        const sr_validate_batch &b = batches[j];
+        if (!b.d_n_records || !b.d_counts || (b.nbytes && !b.d_bytes)) return -EINVAL;
+        if (b.max_records && (!b.d_recs || !b.d_out || b.d_out == b.d_recs)) return -EINVAL;
+        if (b.d_hashes && b.d_hashes_out == b.d_hashes) return -EINVAL;
+        if ((const void *)b.d_counts == (const void *)b.d_n_records) return -EINVAL;   // read after the counts are written
+        if (b.nbytes > 0xFFFFFFF0ull || b.max_records > 0xFFFFFFF0ull) return -EINVAL;
+        if (!b.d_reason) records += b.max_records;
+        tiles += (b.max_records + kValidTile - 1) / kValidTile;
+        const uint64_t likely = (uint64_t)b.nbytes / kValidGridLineBytes + 1u;
+        const uint64_t room = b.max_records < likely ? b.max_records : likely;
+        grid_tiles += (room + kValidTile - 1) / kValidTile;
+    }
+    (void)hipSetDevice(c->device);
+    int rc;
+    if ((rc = grow((void **)&st.d_reason, &st.reason_cap, records, sizeof(uint8_t)))) return rc;
+    if ((rc = grow((void **)&st.d_tiles, &st.tiles_cap, tiles, sizeof(uint4)))) return rc;
+    ValidateArgs a;
+    memset(&a, 0, sizeof(a));
+    size_t at = 0;
+    for (size_t j = 0; j < count; ++j) {
+        const sr_validate_batch &b = batches[j];
+        ValidateBatchArg &o = a.b[j];
+        const bool hashes = b.d_hashes && b.d_hashes_out;
+        o.bytes = b.d_bytes;
+        o.recs = b.d_recs;
+        o.n_records = b.d_n_records;
+        o.hashes = hashes ? b.d_hashes : nullptr;
+        o.out = b.d_out;
+        o.hashes_out = hashes ? b.d_hashes_out : nullptr;
+        o.reason = b.d_reason ? b.d_reason : st.d_reason + at;
+        o.counts = b.d_counts;
+        o.nbytes = (uint32_t)b.nbytes;
+        o.max_records = (uint32_t)b.max_records;
+        if (!b.d_reason) at += b.max_records;
+    }
+    a.hits = st.d_hits;
+    a.tiles = st.d_tiles;
+    a.nb = (uint32_t)count;
+    a.nds = c->ds.nds;
+    a.drop_mask = st.cfg.drop_mask;
+    a.accept_types = st.cfg.accept_types;
+    if (grid_tiles) {
+        const dim3 grid((uint32_t)(grid_tiles < (uint64_t)kValidGroups ? grid_tiles : (uint64_t)kValidGroups));
+        hipLaunchKernelGGL(validate_check_kernel, grid, dim3(kValidBlock), 0, c->stream, a);
+        hipLaunchKernelGGL(validate_scan_kernel, dim3((uint32_t)count), dim3(kValidScanBlock), 0, c->stream, a);
+        hipLaunchKernelGGL(validate_emit_kernel, grid, dim3(kValidBlock), 0, c->stream, a);
+    } else {   // no batch has room for a record: the counts alone
+        hipLaunchKernelGGL(validate_scan_kernel, dim3((uint32_t)count), dim3(kValidScanBlock), 0, c->stream, a);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+int sr_validate_read(sr_ctx *c, sr_validate_hits *hits, size_t n) {
+    static_assert(sizeof(sr_validate_hits) == 2 * sizeof(unsigned long long), "a hit is two cells");
+    if (!c || !c->validate.open || (n && !hits)) return -EINVAL;
+    const size_t m = n < (size_t)SR_VALID_REASONS ? n : (size_t)SR_VALID_REASONS;
+    (void)hipSetDevice(c->device);
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return -EIO;
+    if (m && hipMemcpy(hits, c->validate.d_hits, m * sizeof(sr_validate_hits), hipMemcpyDeviceToHost) != hipSuccess) return -EIO;
+    return (int)m;
+}
+
+int sr_validate_reset(sr_ctx *c) {
+    if (!c || !c->validate.open) return -EINVAL;
+    (void)hipSetDevice(c->device);
+    return hipMemsetAsync(c->validate.d_hits, 0, kValidHitCells * sizeof(unsigned long long), c->stream) == hipSuccess ? 0 : -EIO;
+}
+
+int sr_validate_check(const sr_validate_config *cfg) { return validate_check(cfg); }
+
+int sr_validate_line(const sr_validate_config *cfg, const uint8_t *line, size_t len) {
+    if (validate_check(cfg) != 0 || !line || len == 0) return -EINVAL;
+    return (int)validate_line(line, len, cfg->accept_types);
+}
+
+const char *sr_validate_reason_name(uint32_t reason) { return validate_reason_name(reason); }
+
+int sr_validate_parse_spec(const char *text, sr_validate_config *cfg_out) { return validate_parse_spec(text, cfg_out); }
+
+int sr_set_validate(sr_ctx *c, const sr_validate_config *cfg) {
+    if (!c) return -EINVAL;
+    for (int k = 0; k < 3; ++k)
+        if (c->slot[k].busy) return -EBUSY;
+    if (!cfg) {
+        c->validate_on = 0;
+        return 0;
+    }
+    int rc = validate_check(cfg);   // a bad configuration leaves the stage as it was
+    if (rc) return rc;
+    if (c->validate.open && (rc = sr_validate_close(c))) return rc;
+    if ((rc = sr_validate_open(c, cfg))) return rc;
+    (void)hipSetDevice(c->device);
+    if (!c->d_vcounts && hipMalloc(&c->d_vcounts, 4 * sizeof(uint64_t)) != hipSuccess) {
+        c->d_vcounts = nullptr;
+        return -ENOMEM;
+    }
+    c->validate_on = 1;
+    return 0;
+}
+
+int sr_route_pack_validate(sr_ctx *c, int slot, uint64_t counts[4]) {
+    if (!c || !counts || slot < 0 || slot > 2) return -EINVAL;
+    const sr_ctx::Slot &sl = c->slot[slot];
+    if (sl.busy || !sl.validated || !sl.vhost) return -EBUSY;
+    for (int q = 0; q < 4; ++q) counts[q] = sl.vhost[q];
+    return 0;
+}
+
 // Host outputs of a slot for batches of up to nbytes (grown, never shrunk; the slot is idle).
 static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static int slot_reserve(sr_ctx *c, int k, size_t nbytes) {
@@ -1669,6 +1845,21 @@ static int slot_rules_reserve(sr_ctx *c, int k) {
     return 0;
 }
 
+// sr_set_validate: the slot's counts (the slot is idle): 4 counts and the input's record count
+static int slot_validate_reserve(sr_ctx *c, int k) {
+    sr_ctx::Slot &sl = c->slot[k];
+    if (sl.vhost) return 0;
+    void *h = nullptr, *d = nullptr;
+    if (hipHostMalloc(&h, 64, hipHostMallocMapped) != hipSuccess) return -ENOMEM;
+    if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
+        (void)hipHostFree(h);
+        return -EIO;
+    }
+    sl.vhost = (uint64_t *)h;
+    sl.vdev = (uint64_t *)d;
+    return 0;
+}
+
 // sr_set_logtext: the slot's text arena, index, totals and the staging of prefixes and ends (sized by the
 // switch, which only changes while every slot is idle)
 struct LogLayout {
@@ -1741,6 +1932,8 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
     if (coalesce && (rc = slot_coalesce_reserve(c, k, full))) return rc;
     const bool rules = c->rules_on != 0;
     if (rules && (rc = slot_rules_reserve(c, k))) return rc;
+    const bool validate = c->validate_on != 0;
+    if (validate && (rc = slot_validate_reserve(c, k))) return rc;
     const bool log_trace = c->logtext && c->log_level == 0;   // the formatter needs hashes and datagram ends
     if (log_trace && src && !c->d_ends && hipMalloc(&c->d_ends, (size_t)SR_MAX_SLOTS * sizeof(uint32_t)) != hipSuccess) {
         c->d_ends = nullptr;
@@ -1791,9 +1984,8 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
             hashes = c->d_hash;
         }
         const sr_batch rb{c->d_in, nbytes, c->d_out, cap, hashes, c->d_count, c->d_probed};
-        if (rules) {   // route, rules, coalesce when on, pack: each stage reads the one before's records and count
-            if ((rc = grow((void **)&c->d_rout, &c->d_rout_cap, full, sizeof(sr_record)))) return rc;
-            if (coalesce && (rc = grow((void **)&c->d_rhash, &c->d_rhash_cap, full, sizeof(uint64_t)))) return rc;
+        if (rules || validate) {   // route, validate, rules, coalesce, pack: each stage that is on reads the one
+                                   // before's records, count and (for the coalescing) hashes
             if (coalesce && !c->d_cout && hipMalloc(&c->d_cout, full * sizeof(sr_record)) != hipSuccess) {
                 c->d_cout = nullptr;
                 return -ENOMEM;
@@ -1802,15 +1994,35 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
             DeviceState::add_batch(p, rb.d_bytes, rb.nbytes, rb.d_out, rb.max_records, rb.d_hashes, rb.d_n_records,
                                    rb.d_probed_dead);
             if ((rc = launch_variant(c->ds, p, c->stream))) return rc;
-            const sr_rules_batch ub{c->d_in, nbytes, c->d_out, c->d_count, cap, c->d_rout, coalesce ? c->d_hash : nullptr,
-                                    coalesce ? c->d_rhash : nullptr, nullptr, c->d_rcounts};
-            if ((rc = sr_rules(c, &ub, 1))) return rc;
-            if (coalesce) {
-                const sr_coalesce_batch cb{c->d_in, nbytes, nbytes, c->d_rout, c->d_rcounts, cap, c->d_rhash, c->d_cout, c->d_ccounts};
-                if ((rc = sr_coalesce(c, &cb, 1))) return rc;
+            const sr_record *recs = c->d_out;
+            const uint64_t *cnt = c->d_count, *hs = coalesce ? c->d_hash : nullptr;
+            if (validate) {
+                if ((rc = grow((void **)&c->d_vout, &c->d_vout_cap, full, sizeof(sr_record)))) return rc;
+                if (coalesce && (rc = grow((void **)&c->d_vhash, &c->d_vhash_cap, full, sizeof(uint64_t)))) return rc;
+                const sr_validate_batch vb{c->d_in, nbytes, recs, cnt, cap, c->d_vout, hs, coalesce ? c->d_vhash : nullptr,
+                                           nullptr, c->d_vcounts};
+                if ((rc = sr_validate(c, &vb, 1))) return rc;
+                recs = c->d_vout;
+                cnt = c->d_vcounts;
+                hs = coalesce ? c->d_vhash : nullptr;
             }
-            const sr_pack_batch pb{coalesce ? c->d_cout : c->d_rout, coalesce ? c->d_ccounts : c->d_rcounts, cap, f_in,
-                                   c->d_probed, c->d_sorted, c->d_packets, pcap, c->d_mcounts, f_out};
+            if (rules) {
+                if ((rc = grow((void **)&c->d_rout, &c->d_rout_cap, full, sizeof(sr_record)))) return rc;
+                if (coalesce && (rc = grow((void **)&c->d_rhash, &c->d_rhash_cap, full, sizeof(uint64_t)))) return rc;
+                const sr_rules_batch ub{c->d_in, nbytes, recs, cnt, cap, c->d_rout, hs, coalesce ? c->d_rhash : nullptr,
+                                        nullptr, c->d_rcounts};
+                if ((rc = sr_rules(c, &ub, 1))) return rc;
+                recs = c->d_rout;
+                cnt = c->d_rcounts;
+                hs = coalesce ? c->d_rhash : nullptr;
+            }
+            if (coalesce) {
+                const sr_coalesce_batch cb{c->d_in, nbytes, nbytes, recs, cnt, cap, hs, c->d_cout, c->d_ccounts};
+                if ((rc = sr_coalesce(c, &cb, 1))) return rc;
+                recs = c->d_cout;
+                cnt = c->d_ccounts;
+            }
+            const sr_pack_batch pb{recs, cnt, cap, f_in, c->d_probed, c->d_sorted, c->d_packets, pcap, c->d_mcounts, f_out};
             if ((rc = pack_many_impl(c, &pb, 1, nullptr, nullptr))) return rc;
         } else if (!coalesce) {
             const sr_pack_batch pb{c->d_out, c->d_count, cap, f_in, c->d_probed, c->d_sorted, c->d_packets, pcap,
@@ -1854,8 +2066,9 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
     // input order, and the hashes (sr_route_pack_trace); with the coalescing on coalesce_out_kernel copies them,
     // by the input's count
     // (with the name rules on rules_out_kernel does, unless the coalescing is on too)
-    o.recs = (c->trace && nbytes && !coalesce && !rules) ? c->d_out : nullptr;
-    o.hashes = (c->trace && nbytes && !coalesce && !rules) ? c->d_hash : nullptr;
+    // (and with the line grammar on validate_out_kernel does, unless one of those two is on too)
+    o.recs = (c->trace && nbytes && !coalesce && !rules && !validate) ? c->d_out : nullptr;
+    o.hashes = (c->trace && nbytes && !coalesce && !rules && !validate) ? c->d_hash : nullptr;
     o.h_recs = c->trace ? (sr_record *)sl.tdev : nullptr;
     o.h_hashes = c->trace ? (uint64_t *)(sl.tdev + up256(sl.trec_cap * sizeof(sr_record))) : nullptr;
     // one workgroup per 512 records (two per thread), at most 1024 workgroups (grid-stride beyond)
@@ -1903,6 +2116,26 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
             ro.h_hashes = tr ? (uint64_t *)(sl.tdev + up256(sl.trec_cap * sizeof(sr_record))) : nullptr;
             hipLaunchKernelGGL(rules_out_kernel, dim3((uint32_t)(!tr ? 1 : want < 1024 ? (want ? want : 1) : 1024)),
                                dim3(kRulesBlock), 0, c->stream, ro);
+            if (hipGetLastError() != hipSuccess) return -EIO;
+        }
+    }
+    sl.validated = validate;
+    if (validate) {   // the stage's counts and the input's record count into the slot's page-locked memory
+        if (nbytes == 0) {
+            for (int q = 0; q < 5; ++q) sl.vhost[q] = 0;   // the slot is idle: nothing is in flight that writes here
+        } else {
+            const bool tr = c->trace && !coalesce && !rules;
+            ValidateOut vo;
+            vo.counts = c->d_vcounts;
+            vo.n_records = c->d_count;
+            vo.rec_cap = tr ? sl.trec_cap : 0;
+            vo.h_counts = sl.vdev;
+            vo.recs = tr ? c->d_out : nullptr;
+            vo.hashes = tr ? c->d_hash : nullptr;
+            vo.h_recs = tr ? (sr_record *)sl.tdev : nullptr;
+            vo.h_hashes = tr ? (uint64_t *)(sl.tdev + up256(sl.trec_cap * sizeof(sr_record))) : nullptr;
+            hipLaunchKernelGGL(validate_out_kernel, dim3((uint32_t)(!tr ? 1 : want < 1024 ? (want ? want : 1) : 1024)),
+                               dim3(kValidBlock), 0, c->stream, vo);
             if (hipGetLastError() != hipSuccess) return -EIO;
         }
     }
@@ -1973,6 +2206,7 @@ int sr_route_pack_trace(sr_ctx *c, int slot, const sr_record **records, const ui
     // (and with the name rules on the kept lines')
     const uint64_t nr = (sl.coalesced && sl.chost) ? ((const uint64_t *)(sl.chost + up256(sl.ctext_cap)))[4]
                         : (sl.ruled && sl.rhost)   ? sl.rhost[4]
+                        : (sl.validated && sl.vhost) ? sl.vhost[4]
                                                    : sl.counts[2];
     *n = (size_t)(nr < sl.trec_cap ? nr : sl.trec_cap);
     *records = (const sr_record *)sl.thost;
