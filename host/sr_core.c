@@ -71,6 +71,9 @@ struct sr_core {
     const uint8_t *co_text[2];               /* the merged text of the batch being completed in a slot ... */
     size_t co_base[2];                       /* ... which holds the framed bytes from this offset on       */
     uint64_t co_totals[4];                   /* sr_core_coalesce_counts                                     */
+    int sample;                              /* sr_core_set_sample: hot names thinned on the GPU            */
+    const uint8_t *sa_text[2];               /* the rewritten lines of the batch being completed in a slot ... */
+    size_t sa_base[2];                       /* ... which holds the framed bytes from this offset on        */
     int host_fills;                          /* the host changed pending buffers since the last  */
                                              /* submission: upload them with the next one         */
     uint16_t *fill16;
@@ -253,10 +256,13 @@ static void drop_probed(sr_core *c) {
 
 /* Where framed byte `off` of the batch in `slot` lies: in the framed bytes, or, for a slot batch, in its
  * datagram's slot (the datagram there is its framed form: sr_core_submit_slots wrote the missing '\n').
- * A line, and a datagram, is one run of bytes either way. With sr_core_set_coalesce a record past the batch's
- * bytes is a merged line: it lies in the slot's merged text. */
+ * A line, and a datagram, is one run of bytes either way. With sr_core_set_sample a record in the
+ * SR_SAMPLE_APPEND_CAPACITY(nbytes) bytes past the batch's is a rewritten line: it lies in the slot's sample text.
+ * With sr_core_set_coalesce a record past that (past the batch's bytes, without the sampling) is a merged line: it
+ * lies in the slot's merged text. */
 static const uint8_t *batch_at(const sr_core *c, int slot, const uint8_t *framed, uint32_t off) {
     if (c->co_text[slot] && off >= c->co_base[slot]) return c->co_text[slot] + (off - c->co_base[slot]);
+    if (c->sa_text[slot] && off >= c->sa_base[slot]) return c->sa_text[slot] + (off - c->sa_base[slot]);
     if (!c->slot_n[slot]) return framed + off;
     return sr_slot_addr(c->in[slot], SR_DATA_BUF_SIZE, c->slot_ends[slot], c->slot_n[slot], off);
 }
@@ -350,7 +356,24 @@ static void complete(sr_core *c, int slot, const uint8_t *framed, size_t nbytes,
     memcpy(c->probed, r->probed_dead, c->nwords * sizeof(uint64_t));
     drop_probed(c);
     c->co_text[slot] = NULL;
-    if (c->coalesce) {   /* the merged lines' bytes, behind the batch's own */
+    c->sa_text[slot] = NULL;
+    size_t sa_room = 0;  /* the sample text's room in the device's batch, between the batch and the merged text */
+    if (c->sample) {     /* the rewritten lines' bytes, behind the batch's own */
+        const uint8_t *text = NULL;
+        size_t len = 0;
+        uint64_t counts[4], seed = 0;
+        const int rc = sr_route_pack_sample(c->ctx, slot, &text, &len, counts, &seed);
+        if (rc) {   /* (the text of a routed batch always fits: nothing of this batch can be sent) */
+            core_log(c, SR_ERROR, "%s: sr_route_pack_sample() failed %s", "udp_read_cb", strerror(-rc));
+            c->host_fills = 1;
+            c->dg_n[slot] = 0;
+            return;
+        }
+        c->sa_text[slot] = text;
+        c->sa_base[slot] = nbytes;
+        sa_room = SR_SAMPLE_APPEND_CAPACITY(nbytes);
+    }
+    if (c->coalesce) {   /* the merged lines' bytes, behind the batch's own and the sample text's room */
         const uint8_t *text = NULL;
         size_t len = 0;
         uint64_t counts[4];
@@ -362,7 +385,7 @@ static void complete(sr_core *c, int slot, const uint8_t *framed, size_t nbytes,
             return;
         }
         c->co_text[slot] = text;
-        c->co_base[slot] = nbytes;
+        c->co_base[slot] = nbytes + sa_room;
         for (int q = 0; q < 4; q++) c->co_totals[q] += counts[q];
     }
     /* without the TRACE inputs (the slot was not traced) the WARN lines still come, from the sorted
@@ -706,6 +729,32 @@ int sr_core_validate_hits(sr_core *c, sr_validate_hits *hits, size_t n, int rese
     const int got = sr_validate_read(c->ctx, hits, n);
     if (got < 0) return got;
     if (reset && (rc = sr_validate_reset(c->ctx))) return rc;
+    return got;
+}
+
+int sr_core_set_sample(sr_core *c, const sr_sample_config *cfg) {
+    if (!c) return -EINVAL;
+    if (c->in_flight >= 0) return -EBUSY;
+    int rc = sr_set_sample(c->ctx, cfg);
+    if (rc) return rc;
+    c->sample = cfg ? 1 : 0;
+    c->sa_text[0] = c->sa_text[1] = NULL;
+    /* both slots' text buffers allocated now (an empty batch each; the device's pending bytes carry over); then
+     * the switch once more, so that the first batch of lines is thinned under the configuration's own seed */
+    for (int k = 0; cfg && k < 2; k++) {
+        sr_pack_result r;
+        if ((rc = sr_route_pack_submit(c->ctx, k, NULL, 0, NULL)) || (rc = sr_route_pack_result(c->ctx, k, &r))) return rc;
+    }
+    return cfg ? sr_set_sample(c->ctx, cfg) : 0;
+}
+
+int sr_core_sample_hits(sr_core *c, sr_sample_hits *hits, size_t n, int reset) {
+    if (!c || (n && !hits)) return -EINVAL;
+    int rc = sr_core_drain(c);
+    if (rc) return rc;
+    const int got = sr_sample_read(c->ctx, hits, n);
+    if (got < 0) return got;
+    if (reset && (rc = sr_sample_reset(c->ctx))) return rc;
     return got;
 }
 

@@ -67,6 +67,8 @@ typedef struct sr_config {
                                                 /* line with their sum (sr_core_set_coalesce); off by default         */
     const sr_rules_config *dt_name_rules;       /* SR_NAME_RULES=<path>: the rule file read at start; data lines that */
                                                 /* the set drops are not forwarded (sr_core_set_name_rules); off by default */
+    const sr_sample_config *dt_sample;          /* SR_SAMPLE=<spec>: names over the limit in a batch are thinned and    */
+                                                /* the kept lines marked `|@<rate>` (sr_core_set_sample); off by default */
     const sr_validate_config *dt_validate;      /* SR_VALIDATE=<spec>: data lines whose reason the spec drops are not */
                                                 /* forwarded, every reason is counted (sr_core_set_validate); off by default */
     int dt_yield;                               /* full batches per read event before timers run (0: no cap) */

@@ -353,6 +353,28 @@ static void log_validate(data_thread *d) {
     sr_log(SR_INFO, "validate: dropped lines=%llu bytes=%llu%s", (unsigned long long)lines, (unsigned long long)bytes, text);
 }
 
+/* SR_SAMPLE=<spec>: the sampleable lines the thread saw and those it dropped since its last ping, and per rate
+ * (the steps that were taken, in order) the lines seen and kept; then the hits start again. */
+static void log_sample(data_thread *d) {
+    sr_sample_hits hits[SR_SAMPLE_STEPS];
+    const int n = sr_core_sample_hits(d->core, hits, SR_SAMPLE_STEPS, 1);
+    if (n < 0) {
+        sr_log(SR_ERROR, "%s: sr_core_sample_hits() failed %s", "ping_cb", strerror(-n));
+        return;
+    }
+    uint64_t seen = 0, kept = 0;
+    char text[SR_SAMPLE_STEPS * 56] = "";
+    size_t used = 0;
+    for (int i = 0; i < n; i++) {
+        seen += hits[i].seen;
+        kept += hits[i].kept;
+        if (i == 0 || !hits[i].seen || used >= sizeof(text)) continue;
+        used += (size_t)snprintf(text + used, sizeof(text) - used, " %s=%llu/%llu", sr_sample_rate_text((uint32_t)i),
+                                 (unsigned long long)hits[i].seen, (unsigned long long)hits[i].kept);
+    }
+    sr_log(SR_INFO, "sample: seen=%llu dropped=%llu%s", (unsigned long long)seen, (unsigned long long)(seen - kept), text);
+}
+
 /* SR_NAME_STATS=1: what the thread routed since its last ping, then the statistics start again. A thread that
  * routed no valid line logs nothing. */
 #define NAME_STATS_HOT_LINES 8
@@ -391,6 +413,7 @@ static void ping_timer_cb(struct ev_loop *loop, ev_periodic *p, int revents) {
     if (d->c->dt_name_stats) log_name_stats(d);
     if (d->c->dt_name_rules) log_name_rules(d);
     if (d->c->dt_validate) log_validate(d);
+    if (d->c->dt_sample) log_sample(d);
 }
 
 /* a data thread that cannot route: the process ends (status 1) unless SR_REQUIRE_GPU=0 */
@@ -470,6 +493,10 @@ void *sr_data_thread(void *arg) {
     }
     if (c->dt_name_rules && (rc = sr_core_set_name_rules(d->core, c->dt_name_rules))) {
         sr_log(SR_ERROR, "%s: sr_core_set_name_rules() failed %s", fn, strerror(-rc));
+        return thread_fail(d, 1);
+    }
+    if (c->dt_sample && (rc = sr_core_set_sample(d->core, c->dt_sample))) {
+        sr_log(SR_ERROR, "%s: sr_core_set_sample() failed %s", fn, strerror(-rc));
         return thread_fail(d, 1);
     }
     if (c->dt_coalesce) {
@@ -613,6 +640,16 @@ int main(int argc, char *argv[]) {
         }
         sr_log(SR_INFO, "%s: validate: %s", "main", vs);
         config.dt_validate = &validate;
+    }
+    const char *ss = getenv("SR_SAMPLE");
+    if (ss && ss[0]) {   /* a bad spec is a config error */
+        static sr_sample_config sample;   /* lives as long as the process */
+        if (sr_sample_parse_spec(ss, &sample) != 0) {
+            sr_log(SR_ERROR, "%s: SR_SAMPLE %s: not <limit> or <limit>:<comma list of c, ms, h, d>", "main", ss);
+            exit(1);
+        }
+        sr_log(SR_INFO, "%s: sample: %s", "main", ss);
+        config.dt_sample = &sample;
     }
     config.dt_yield = dy ? atoi(dy) : 0;
     config.dt_yield_s = dys ? atof(dys) : READ_EVENT_SECONDS;

@@ -1148,6 +1148,162 @@ int sr_validate_parse_spec(const char *text, sr_validate_config *cfg_out);
 int sr_set_validate(sr_ctx *ctx, const sr_validate_config *cfg_or_null);
 int sr_route_pack_validate(sr_ctx *ctx, int slot, uint64_t counts[4]);
 
+/* ---- sample rates on the device: thin hot timers the way a client would have ----------------------- */
+/* Timers, histograms and distributions (|ms, |h, |d) cannot be added together as sr_coalesce adds plain counters,
+ * and a hot name of them overloads its shard all the same. Every statsd has one answer: send one line in k and
+ * mark it `|@<1/k>`, so that the server scales the counts back. This stage does that for clients that do not: it
+ * counts the lines per name in a batch, thins the names that exceed a limit, and writes the kept lines with the
+ * sample rate inserted. It consumes the input-order records and the hashes of a route launch and writes a shorter
+ * record list, as sr_rules and sr_validate do; sr_coalesce and the packing run unchanged on the result. A sampled
+ * `|c` line carries an '@' and so is no longer a plain counter: sr_coalesce does not merge it. Exact and
+ * deterministic (tests/sample_expect.py restates it).
+ *
+ * Subject records: a record (o, L, r) is subject iff r < n_downstreams, L >= 1 and o + L <= nbytes (sr_rules'
+ *   rule). No byte outside [0, nbytes) is ever read.
+ * Sampleable: a subject record is sampleable iff all of the following hold:
+ *   1. 6 <= L <= SR_SAMPLE_LINE_MAX (1441 = 1449 - SR_SAMPLE_EXTRA_MAX) and the last byte is '\n'. The content C
+ *      is the first L - 1 bytes.
+ *   2. p = the index of the first ':' in C, and p >= 1.
+ *   3. q = the index of the first '|' in C[p+1:], as an index into C. It exists and q > p + 1 (a value of at
+ *      least one byte).
+ *   4. e = the index of the next '|' behind q, or len(C) when there is none. C[q+1:e] is exactly one of c, ms, h,
+ *      d, and that type's bit (SR_VALID_TYPE_C, _MS, _H, _D) is set in the configuration's `types`.
+ *   5. Either e == len(C), or e + 1 < len(C) and C[e+1] == '#'.
+ *   So a line that already carries an '@' section is not sampleable, nor is one with an empty or unknown type.
+ *   Name bytes, the value's shape and the tags are not judged: that is sr_validate's work, which runs before this
+ *   stage. Every record that is not sampleable passes through untouched. ins = e is the insertion point.
+ * Count: with S slots per batch the slot of a sampleable record i is fmix64(hash_i) & (S - 1), fmix64 being the
+ *   MurmurHash3 finaliser that the name statistics use and hash_i = d_hashes[i] as given (never recomputed).
+ *   c(slot) is the number of sampleable records of the batch in that slot. No names are compared: names that share
+ *   a slot share a count and a budget. That is harmless here, because every kept line still carries the rate by
+ *   which its own slot was thinned, so the server's scaled counts stay unbiased per line.
+ * Step: the ladder K is 1, 2, 5, 10, 20, 50, 100, 200, 500, 1000, 2000, 5000, 10000 (SR_SAMPLE_STEPS entries) and
+ *   the rate texts R are "", 0.5, 0.2, 0.1, 0.05, 0.02, 0.01, 0.005, 0.002, 0.001, 0.0005, 0.0002, 0.0001. The
+ *   step j of a sampleable record is the smallest j with c <= (u64)limit * K[j]; without such a j it is 12.
+ * Keep: a sampleable record with j == 0 is kept as it is. With j >= 1 record i (its index in the stage's input)
+ *   is kept iff ((u >> 32) * K[j]) >> 32 == 0 with u = fmix64(hash_i ^ (seed + i * 0x9E3779B97F4A7C15)), all modulo
+ *   2^64, and seed = cfg.seed + batch.seed_add. A Bernoulli draw per line, as a client makes it; deterministic for
+ *   a seed and independent of the order of execution.
+ * Output: d_out receives, in input order, the records that are not sampleable and the kept records of step 0 as
+ *   they were, nothing for the dropped ones, and for a kept record of step j >= 1
+ *   {offset = nbytes + a, length = L + 2 + len(R[j]), route}: its text line[0:ins] + "|@" + R[j] + line[ins:L] is
+ *   written to d_bytes + nbytes + a, a being the total length of the rewritten lines of earlier records. When
+ *   d_hashes_out is given the hashes are compacted alongside (so sr_coalesce can follow). The optional d_step (u8
+ *   per input record) receives SR_SAMPLE_NOT_SAMPLEABLE, or j with bit 7 set when the record was dropped.
+ *   d_counts: four u64 {records out, records dropped, lines rewritten, appended bytes needed}; &d_counts[0] is
+ *   what the next stage takes as d_n_records. Of the text the first min(d_counts[3], append_cap) bytes are
+ *   written, nothing at or past append_cap; the text is complete iff d_counts[3] <= append_cap (an offset is
+ *   taken modulo 2^32, which only an incomplete text can reach). Of a batch the first
+ *   min(*d_n_records, max_records) records are read.
+ *   SR_SAMPLE_APPEND_CAPACITY(nbytes) = nbytes + (nbytes / 6) * 8 always suffices for records that do not
+ *   overlap: the rewritten lines are lines of the batch, together at most nbytes bytes, each of them has at least
+ *   6 bytes, so there are at most nbytes / 6 of them, and each grows by at most SR_SAMPLE_EXTRA_MAX = 8 bytes
+ *   ("|@0.0001").
+ * Hits: the context keeps {seen, kept} as u64 per step, SR_SAMPLE_STEPS pairs, accumulated over all calls since
+ *   sr_sample_open or the last sr_sample_reset.
+ * Configuration: slots 0 selects SR_SAMPLE_DEFAULT_SLOTS, otherwise a power of two in SR_SAMPLE_MIN_SLOTS ..
+ *   SR_SAMPLE_MAX_SLOTS; limit >= 1; types non-zero and within C | MS | H | D; reserved 0. Anything else -EINVAL.
+ *
+ * sr_sample_open : allocates the table (slots u32 for each of SR_MAX_BATCHES_PER_LAUNCH batches) and the hits;
+ *   not inside stream capture. 0, -EINVAL, -EBUSY (the stage is open), -ENOMEM.
+ * sr_sample      : count in 1..SR_MAX_BATCHES_PER_LAUNCH batches, asynchronous on the context's stream. Scratch
+ *   is allocated on the first call or a larger one; later calls allocate nothing and can be captured in a graph.
+ *   -EINVAL before any launch for a null required pointer (d_n_records, d_counts, d_hashes; d_recs and d_out with
+ *   max_records > 0; d_bytes with nbytes > 0 or append_cap > 0), d_out == d_recs, d_hashes_out == d_hashes,
+ *   d_counts == d_n_records, nbytes > SR_SAMPLE_MAX_BYTES (2^30), nbytes + append_cap > 0xFFFFFFF0,
+ *   max_records > 0xFFFFFFF0, a bad count or a stage that is not open. Alignment as sr_validate (d_step: any).
+ * sr_sample_read : waits for the stream and copies the first min(n, SR_SAMPLE_STEPS) pairs; returns how many.
+ * sr_sample_reset: zeroes the hits, in stream order.
+ * sr_sample_close: waits for the stream and frees the stage (sr_close does it too). 0, -EINVAL, -EBUSY.
+ *
+ * Host only (no GPU):
+ *   sr_sample_check     : 0 or -EINVAL for a configuration;
+ *   sr_sample_parse     : 1 when the line of `len` bytes is sampleable under `types` (*ins and *type_bit are then
+ *     set), else 0; -EINVAL for a null line;
+ *   sr_sample_step      : the step for a limit and a count;
+ *   sr_sample_keep      : 1 or 0, the keep rule (step >= SR_SAMPLE_STEPS: -EINVAL);
+ *   sr_sample_rate_text : R[step], NULL for any other number;
+ *   sr_sample_rewrite   : writes line[0:ins] + "|@" + R[step] + line[ins:len] to dst and returns its length (dst has
+ *     len + SR_SAMPLE_EXTRA_MAX bytes of room; 0 for step == 0, step >= SR_SAMPLE_STEPS or ins > len);
+ *   sr_sample_parse_spec: `<limit>` or `<limit>:<comma list of c, ms, h, d>` into *cfg_out; the default types are
+ *     ms, h, d, the seed is 0 and the slots are the default; anything else is -EINVAL. */
+#define SR_SAMPLE_STEPS          13u
+#define SR_SAMPLE_EXTRA_MAX      8u
+#define SR_SAMPLE_LINE_MAX       1441u
+#define SR_SAMPLE_NOT_SAMPLEABLE 0xFFu
+#define SR_SAMPLE_DROPPED        0x80u
+#define SR_SAMPLE_DEFAULT_SLOTS  65536u
+#define SR_SAMPLE_MIN_SLOTS      16u
+#define SR_SAMPLE_MAX_SLOTS      (1u << 22)
+#define SR_SAMPLE_MAX_BYTES      ((size_t)1 << 30)
+#define SR_SAMPLE_TYPES_ALL      (1u | 4u | 8u | 32u)   /* SR_VALID_TYPE_C | _MS | _H | _D */
+#define SR_SAMPLE_APPEND_CAPACITY(nbytes) ((size_t)(nbytes) + ((size_t)(nbytes) / 6u) * 8u)
+
+typedef struct sr_sample_config {
+    uint32_t slots;      /* 0: SR_SAMPLE_DEFAULT_SLOTS                        */
+    uint32_t limit;      /* lines of one slot a batch keeps at full rate, >= 1 */
+    uint32_t types;      /* SR_VALID_TYPE_C | _MS | _H | _D bits               */
+    uint32_t reserved;   /* 0                                                  */
+    uint64_t seed;
+} sr_sample_config;
+
+typedef struct sr_sample_batch {
+    uint8_t *d_bytes; size_t nbytes;              /* the routed batch; the rewritten lines go behind it    */
+    size_t append_cap;                            /* room behind d_bytes + nbytes                          */
+    const sr_record *d_recs;                      /* input-order records (sr_batch.d_out)                  */
+    const uint64_t *d_n_records; size_t max_records;
+    const uint64_t *d_hashes;                     /* max_records u64 (sr_batch.d_hashes); required         */
+    sr_record *d_out;                             /* max_records records; not d_recs                       */
+    uint64_t *d_hashes_out;                       /* optional: the hashes, compacted alongside             */
+    uint8_t *d_step;                              /* optional: max_records u8, the record's step           */
+    uint64_t *d_counts;                           /* 4 u64: out, dropped, rewritten, appended bytes needed */
+    uint64_t seed_add;                            /* added to the configuration's seed                     */
+} sr_sample_batch;
+
+typedef struct sr_sample_hits {
+    uint64_t seen, kept;
+} sr_sample_hits;
+
+int sr_sample_open(sr_ctx *ctx, const sr_sample_config *cfg);
+int sr_sample_close(sr_ctx *ctx);
+int sr_sample(sr_ctx *ctx, const sr_sample_batch *batches, size_t count);
+int sr_sample_read(sr_ctx *ctx, sr_sample_hits *hits, size_t n);
+int sr_sample_reset(sr_ctx *ctx);
+int sr_sample_check(const sr_sample_config *cfg);
+int sr_sample_parse(const uint8_t *line, size_t len, uint32_t types, uint32_t *ins, uint32_t *type_bit);
+uint32_t sr_sample_step(uint32_t limit, uint64_t c);
+int sr_sample_keep(uint64_t hash, uint64_t seed, uint64_t index, uint32_t step);
+const char *sr_sample_rate_text(uint32_t step);
+size_t sr_sample_rewrite(uint8_t *dst, const uint8_t *line, size_t len, uint32_t ins, uint32_t step);
+int sr_sample_parse_spec(const char *text, sr_sample_config *cfg_out);
+
+/* The sample rates of the host-memory path. With sr_set_sample(ctx, cfg) (the stage is opened with cfg; an open
+ * stage is closed first, hits included) every later sr_route_pack_submit / sr_route_pack_submit_slots /
+ * sr_route_pack_batch runs the route launch, then sr_validate when sr_set_validate is on, then sr_rules when
+ * sr_set_name_rules is on, then sr_sample, then sr_coalesce when sr_set_coalesce is on, then the packing: each
+ * stage reads the one before's records, count and hashes. Sampling stands before the coalescing because sr_coalesce
+ * does not hand hashes on; a sampled `|c` line is no longer a plain counter and is not merged.
+ * The context's input buffer is allocated again with SR_SAMPLE_APPEND_CAPACITY(max_batch_bytes) of room behind the
+ * batch, and the coalescing's max_batch_bytes behind that when both are (or were) on: a batch's rewritten lines lie
+ * at d_in + nbytes, sr_coalesce takes nbytes + SR_SAMPLE_APPEND_CAPACITY(nbytes) as its nbytes and writes its merged
+ * text behind that, and the payload gather (sr_set_payloads) takes the whole as its batch. Records in `sorted`
+ * with offset in [nbytes, nbytes + SR_SAMPLE_APPEND_CAPACITY(nbytes)) point into the rewritten text, at
+ * offset - nbytes; those behind it into the merged text. seed_add is the number of submissions accepted on the
+ * context since sr_set_sample (empty ones included), so the first uses cfg.seed and successive batches thin
+ * different positions. `sorted`, `packets`, `fill`, n_records and n_valid describe the thinned batch (whose lines
+ * may be up to SR_SAMPLE_EXTRA_MAX bytes longer: the slots' packets and payloads are sized for it). The trace
+ * (sr_route_pack_trace), the log text and the name statistics keep the route launch's records: logs and
+ * statistics are byte-identical to the switch being off. NULL turns the switch off (the stage and its hits stay
+ * until sr_sample_close). Off by default: nothing is allocated, launched or copied.
+ * Returns 0, -EINVAL (a bad configuration, max_batch_bytes > SR_SAMPLE_MAX_BYTES, or a buffer that would pass
+ * 0xFFFFFFF0 bytes), -ENOMEM, -EBUSY (a slot is in flight).
+ * sr_route_pack_sample: after sr_route_pack_result(slot) (for sr_route_pack_batch: slot 2), a page-locked copy of
+ * the batch's rewritten text (*len bytes, valid until the slot's next submission), the stage's four counts and the
+ * seed the batch was thinned under (cfg.seed + seed_add). -EBUSY when the slot is in flight or was submitted with
+ * the switch off. */
+int sr_set_sample(sr_ctx *ctx, const sr_sample_config *cfg_or_null);
+int sr_route_pack_sample(sr_ctx *ctx, int slot, const uint8_t **text, size_t *len, uint64_t counts[4], uint64_t *seed);
+
 /* ---- owner side of the multi-GPU regroup: received lines into packets ------------------------------ */
 /* After sr_regroup_launch / sr_regroup_run the lines of the shards a GPU owns lie in d_recv_bytes /
  * d_recv_recs: every source's chunk in source order 0, 1, ..., each chunk batch 0's lines, then batch

@@ -214,6 +214,23 @@ int sr_core_name_rule_hits(sr_core *core, sr_rule_hits *hits, size_t n, int rese
 int sr_core_set_validate(sr_core *core, const sr_validate_config *cfg_or_null);
 int sr_core_validate_hits(sr_core *core, sr_validate_hits *hits, size_t n, int reset);
 
+/* Sample rates. With sr_core_set_sample(core, cfg) (cfg as sr_sample_open takes it, sr_route.h) every later batch of
+ * sr_core_route*, sr_core_submit* and sr_core_submit_slots has the names that exceed cfg->limit lines in the batch
+ * thinned on the GPU, after the line grammar and the name rules and before the coalescing when those switches are on
+ * too (sr_set_sample): of such a name one line in K is kept, and a kept line leaves with `|@<1/K>` inserted behind
+ * its type. The first batch is thinned under cfg->seed, the next under cfg->seed + 1, and so on. The log lines and
+ * the name statistics are those of the switch being off; packets, traffic counters and pending bytes describe the
+ * thinned batch. A packet's line lies in the batch, in the sample text (a rewritten line) or in the merged text
+ * (sr_core_set_coalesce). Ping lines are routed outside the submit path and are never sampled. NULL turns the switch
+ * off. A new configuration starts the hits again from zero.
+ * sr_core_sample_hits: drains first, then copies the first min(n, SR_SAMPLE_STEPS) pairs {seen, kept} per step since
+ * the configuration was given or the last reset, and returns how many it copied; reset != 0 starts them again
+ * from zero.
+ * Return 0 (hits: the count), -EINVAL (also: hits before the switch was ever on), -EBUSY (set: a batch is in
+ * flight, drain first), -ENOMEM, -EIO. */
+int sr_core_set_sample(sr_core *core, const sr_sample_config *cfg_or_null);
+int sr_core_sample_hits(sr_core *core, sr_sample_hits *hits, size_t n, int reset);
+
 /* Test hook (fault injection; nothing calls it in the executable): the fail_submit-th call of
  * sr_core_submit* fails as a failed sr_route_pack_submit (the batch is not taken), and the
  * fail_finish-th batch to complete fails as a failed sr_route_pack_result (its packets and log lines

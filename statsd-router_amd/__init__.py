@@ -67,6 +67,9 @@ ABI_FUNCTIONS = (
     "sr_rules_parse_text", "sr_rules_free", "sr_set_name_rules", "sr_route_pack_rules",
     "sr_validate_open", "sr_validate_close", "sr_validate", "sr_validate_read", "sr_validate_reset", "sr_validate_check",
     "sr_validate_line", "sr_validate_reason_name", "sr_validate_parse_spec", "sr_set_validate", "sr_route_pack_validate",
+    "sr_sample_open", "sr_sample_close", "sr_sample", "sr_sample_read", "sr_sample_reset", "sr_sample_check",
+    "sr_sample_parse", "sr_sample_step", "sr_sample_keep", "sr_sample_rate_text", "sr_sample_rewrite",
+    "sr_sample_parse_spec", "sr_set_sample", "sr_route_pack_sample",
 )
 SR_LOG_MAX_PREFIX = 256
 SR_LOG_TRACE, SR_LOG_WARN = 0, 3   # sr_log_batch.min_level and the d_levels values
@@ -373,6 +376,93 @@ def validate_parse_spec(text: str) -> ValidateConfig:
     return ValidateConfig(cfg.drop_mask, cfg.accept_types)
 
 
+class SrSampleConfig(ctypes.Structure):
+    """struct sr_sample_config (include/sr_route.h)."""
+    _fields_ = [("slots", ctypes.c_uint32), ("limit", ctypes.c_uint32), ("types", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("seed", ctypes.c_uint64)]
+
+
+class SrSampleBatch(ctypes.Structure):
+    """struct sr_sample_batch (include/sr_route.h): one routed batch of sr_sample."""
+    _fields_ = [("d_bytes", ctypes.c_void_p), ("nbytes", ctypes.c_size_t), ("append_cap", ctypes.c_size_t),
+                ("d_recs", ctypes.c_void_p), ("d_n_records", ctypes.c_void_p), ("max_records", ctypes.c_size_t),
+                ("d_hashes", ctypes.c_void_p), ("d_out", ctypes.c_void_p), ("d_hashes_out", ctypes.c_void_p),
+                ("d_step", ctypes.c_void_p), ("d_counts", ctypes.c_void_p), ("seed_add", ctypes.c_uint64)]
+
+
+class SrSampleHits(ctypes.Structure):
+    """struct sr_sample_hits (include/sr_route.h)."""
+    _fields_ = [("seen", ctypes.c_uint64), ("kept", ctypes.c_uint64)]
+
+
+SR_SAMPLE_STEPS, SR_SAMPLE_EXTRA_MAX, SR_SAMPLE_LINE_MAX = 13, 8, 1441
+SR_SAMPLE_NOT_SAMPLEABLE, SR_SAMPLE_DROPPED = 0xFF, 0x80
+SR_SAMPLE_DEFAULT_SLOTS, SR_SAMPLE_MIN_SLOTS, SR_SAMPLE_MAX_SLOTS = 65536, 16, 1 << 22
+SR_SAMPLE_MAX_BYTES = 1 << 30
+SR_SAMPLE_TYPES_ALL = SR_VALID_TYPE_C | SR_VALID_TYPE_MS | SR_VALID_TYPE_H | SR_VALID_TYPE_D
+SAMPLE_TILE = 256   # kSampleTile (csrc/sample_kernel.hpp): records per tile of the sample kernels
+
+
+def sample_append_capacity(nbytes: int) -> int:
+    """SR_SAMPLE_APPEND_CAPACITY: room behind the batch that always suffices for records that do not overlap."""
+    return nbytes + (nbytes // 6) * 8
+
+
+class SampleConfig:
+    """A sr_sample_config: the slots (0: the default), the limit per slot and batch, the types and the seed."""
+
+    def __init__(self, limit: int, types: int = SR_VALID_TYPE_MS | SR_VALID_TYPE_H | SR_VALID_TYPE_D, slots: int = 0,
+                 seed: int = 0, reserved: int = 0):
+        self.limit, self.types, self.slots, self.seed = int(limit), int(types), int(slots), int(seed)
+        self.cfg = SrSampleConfig(self.slots, self.limit, self.types, int(reserved), self.seed)
+
+    def ref(self):
+        return ctypes.byref(self.cfg)
+
+    def check(self) -> int:
+        """sr_sample_check: 0 or a negative errno."""
+        return int(lib().sr_sample_check(self.ref()))
+
+
+def sample_parse(line: bytes, types: int = SR_SAMPLE_TYPES_ALL):
+    """sr_sample_parse: (ins, type bit) of a sampleable line ('\n' included), None for any other."""
+    buf = (ctypes.c_uint8 * max(len(line), 1)).from_buffer_copy(line or b"\0")
+    ins, bit = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    rc = _check(lib().sr_sample_parse(buf, len(line), types, ctypes.byref(ins), ctypes.byref(bit)), "sr_sample_parse")
+    return (ins.value, bit.value) if rc else None
+
+
+def sample_step(limit: int, count: int) -> int:
+    """sr_sample_step: the ladder's step for a limit and a slot's count."""
+    return int(lib().sr_sample_step(limit, count))
+
+
+def sample_keep(name_hash: int, seed: int, index: int, step: int) -> bool:
+    """sr_sample_keep: whether record `index` of a batch is kept at `step`."""
+    return bool(_check(lib().sr_sample_keep(name_hash, seed, index, step), "sr_sample_keep"))
+
+
+def sample_rate_text(step: int):
+    """sr_sample_rate_text: the step's rate as the rewritten line carries it, None for a number that is no step."""
+    text = lib().sr_sample_rate_text(step)
+    return text.decode() if text is not None else None
+
+
+def sample_rewrite(line: bytes, ins: int, step: int) -> bytes:
+    """sr_sample_rewrite: the line with `|@<rate>` inserted at ins (empty for step 0 or a bad argument)."""
+    src = (ctypes.c_uint8 * max(len(line), 1)).from_buffer_copy(line or b"\0")
+    dst = (ctypes.c_uint8 * (len(line) + SR_SAMPLE_EXTRA_MAX))()
+    n = int(lib().sr_sample_rewrite(dst, src, len(line), ins, step))
+    return bytes(dst[:n])
+
+
+def sample_parse_spec(text: str) -> SampleConfig:
+    """sr_sample_parse_spec: `<limit>` or `<limit>:<comma list of c, ms, h, d>` into a SampleConfig."""
+    cfg = SrSampleConfig()
+    _check(lib().sr_sample_parse_spec(text.encode(), ctypes.byref(cfg)), "sr_sample_parse_spec")
+    return SampleConfig(cfg.limit, cfg.types, cfg.slots, cfg.seed)
+
+
 class SrStatsSnapshot(ctypes.Structure):
     """struct sr_stats_snapshot (include/sr_route.h)."""
     _fields_ = [("cfg", SrStatsConfig), ("n_downstreams", ctypes.c_uint32), ("hot_overflow", ctypes.c_uint32),
@@ -656,6 +746,21 @@ def _load_route_lib() -> ctypes.CDLL:
         "sr_validate_parse_spec": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(SrValidateConfig)]),
         "sr_set_validate": (ctypes.c_int, [vp, ctypes.POINTER(SrValidateConfig)]),
         "sr_route_pack_validate": (ctypes.c_int, [vp, ctypes.c_int, u64p]),
+        "sr_sample_open": (ctypes.c_int, [vp, ctypes.POINTER(SrSampleConfig)]),
+        "sr_sample_close": (ctypes.c_int, [vp]),
+        "sr_sample": (ctypes.c_int, [vp, ctypes.POINTER(SrSampleBatch), ctypes.c_size_t]),
+        "sr_sample_read": (ctypes.c_int, [vp, ctypes.POINTER(SrSampleHits), ctypes.c_size_t]),
+        "sr_sample_reset": (ctypes.c_int, [vp]),
+        "sr_sample_check": (ctypes.c_int, [ctypes.POINTER(SrSampleConfig)]),
+        "sr_sample_parse": (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+                                           ctypes.POINTER(ctypes.c_uint32)]),
+        "sr_sample_step": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint64]),
+        "sr_sample_keep": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]),
+        "sr_sample_rate_text": (ctypes.c_char_p, [ctypes.c_uint32]),
+        "sr_sample_rewrite": (ctypes.c_size_t, [vp, vp, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32]),
+        "sr_sample_parse_spec": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(SrSampleConfig)]),
+        "sr_set_sample": (ctypes.c_int, [vp, ctypes.POINTER(SrSampleConfig)]),
+        "sr_route_pack_sample": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(vp), c_size_p, u64p, u64p]),
     }
     for name in ABI_FUNCTIONS:
         if os.environ.get("SR_ROUTE_LIB") and not hasattr(lib, name):
@@ -1208,6 +1313,55 @@ class Router:
         counts = (ctypes.c_uint64 * 4)()
         _check(self._lib.sr_route_pack_validate(self._h, slot, counts), "sr_route_pack_validate")
         return np.array(list(counts), np.uint64)
+
+    def sample_open(self, cfg: SampleConfig) -> None:
+        """sr_sample_open: the sample-rate stage of this context."""
+        _check(self._lib.sr_sample_open(self._h, cfg.ref()), "sr_sample_open")
+
+    def sample_close(self) -> None:
+        _check(self._lib.sr_sample_close(self._h), "sr_sample_close")
+
+    @staticmethod
+    def sample_batches(batches):
+        """The sr_sample_batch array of [(d_bytes, nbytes, append_cap, d_recs, d_n_records, max_records, d_hashes,
+        d_out, d_hashes_out, d_step, d_counts, seed_add), ...] (raw device addresses; 0 = NULL)."""
+        arr = (SrSampleBatch * max(len(batches), 1))()
+        for i, (db, nb, cap, dr, dn, mr, dh, do, dho, dst, dc, sa) in enumerate(batches):
+            arr[i] = SrSampleBatch(db or None, nb, cap, dr or None, dn or None, mr, dh or None, do or None, dho or None,
+                                   dst or None, dc or None, sa)
+        return arr
+
+    def sample(self, batches) -> None:
+        """sr_sample over the batches of one route launch (as sample_batches takes them, or its array),
+        asynchronous on the context's stream."""
+        arr = batches if isinstance(batches, ctypes.Array) else self.sample_batches(batches)
+        _check(self._lib.sr_sample(self._h, arr, len(batches)), "sr_sample")
+
+    def sample_read(self, n: int | None = None) -> np.ndarray:
+        """sr_sample_read: the hits as an array of [seen, kept] rows, one per step."""
+        n = SR_SAMPLE_STEPS if n is None else n
+        hits = (SrSampleHits * max(n, 1))()
+        m = _check(self._lib.sr_sample_read(self._h, hits, n), "sr_sample_read")
+        return np.array([[hits[i].seen, hits[i].kept] for i in range(m)], np.uint64).reshape(m, 2)
+
+    def sample_reset(self) -> None:
+        _check(self._lib.sr_sample_reset(self._h), "sr_sample_reset")
+
+    def set_sample(self, cfg: SampleConfig | None) -> None:
+        """sr_set_sample: later route_pack submissions thin the names over the limit and mark the kept lines with
+        the sample rate, between the name rules and the coalescing (None: off)."""
+        _check(self._lib.sr_set_sample(self._h, cfg.ref() if cfg is not None else None), "sr_set_sample")
+
+    def route_pack_sample(self, slot: int):
+        """sr_route_pack_sample after route_pack_result(slot) (route_pack: slot 2): (rewritten text, counts[4]: out,
+        dropped, rewritten, text bytes needed; the seed the batch was thinned under)."""
+        text, n = ctypes.c_void_p(), ctypes.c_size_t()
+        counts = (ctypes.c_uint64 * 4)()
+        seed = ctypes.c_uint64()
+        _check(self._lib.sr_route_pack_sample(self._h, slot, ctypes.byref(text), ctypes.byref(n), counts, ctypes.byref(seed)),
+               "sr_route_pack_sample")
+        raw = bytes((ctypes.c_uint8 * n.value).from_address(text.value)) if n.value else b""
+        return raw, np.array(list(counts), np.uint64), int(seed.value)
 
     def route_pack_submit_slots(self, slot: int, slots, stride: int, lens, fill=None) -> None:
         """sr_route_pack_submit_slots (asynchronous): `slots` is page-locked memory (a HostBuffer, or its

@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from . import SR_VALID_REASONS, SrValidateConfig, SrValidateHits
+from . import SR_SAMPLE_STEPS, SR_VALID_REASONS, SrSampleConfig, SrSampleHits, SrValidateConfig, SrValidateHits
 from . import LIB_DIR, SR_RULES_MAX, SrCoalesceConfig, SrError, SrRuleHits, SrRulesConfig, SrStatsConfig, SrStatsSnapshot, StatsSnapshot, _check, alive_words, lib
 
 ROUTER_LIB = os.path.join(LIB_DIR, "libsr_router.so")
@@ -91,6 +91,10 @@ def router_lib() -> ctypes.CDLL:
         L.sr_core_name_rule_hits.argtypes = [vp, ctypes.POINTER(SrRuleHits), ctypes.c_size_t, ctypes.c_int]
         L.sr_core_set_validate.restype = ctypes.c_int
         L.sr_core_set_validate.argtypes = [vp, ctypes.POINTER(SrValidateConfig)]
+        L.sr_core_set_sample.restype = ctypes.c_int
+        L.sr_core_set_sample.argtypes = [vp, ctypes.POINTER(SrSampleConfig)]
+        L.sr_core_sample_hits.restype = ctypes.c_int
+        L.sr_core_sample_hits.argtypes = [vp, ctypes.POINTER(SrSampleHits), ctypes.c_size_t, ctypes.c_int]
         L.sr_core_validate_hits.restype = ctypes.c_int
         L.sr_core_validate_hits.argtypes = [vp, ctypes.POINTER(SrValidateHits), ctypes.c_size_t, ctypes.c_int]
         L.sr_core_device_log_stats.restype = ctypes.c_int
@@ -270,6 +274,17 @@ class Core:
     def set_validate(self, cfg) -> None:
         """sr_core_set_validate: later batches lose the lines whose reason the ValidateConfig drops (None: off)."""
         _check(self._L.sr_core_set_validate(self._h, cfg.ref() if cfg is not None else None), "sr_core_set_validate")
+
+    def set_sample(self, cfg) -> None:
+        """sr_core_set_sample: later batches have the names over the SampleConfig's limit thinned and the kept lines
+        marked with the sample rate (None: off)."""
+        _check(self._L.sr_core_set_sample(self._h, cfg.ref() if cfg is not None else None), "sr_core_set_sample")
+
+    def sample_hits(self, reset: bool = False) -> np.ndarray:
+        """sr_core_sample_hits: drains, then [seen, kept] per step."""
+        hits = (SrSampleHits * SR_SAMPLE_STEPS)()
+        m = _check(self._L.sr_core_sample_hits(self._h, hits, SR_SAMPLE_STEPS, 1 if reset else 0), "sr_core_sample_hits")
+        return np.array([[hits[i].seen, hits[i].kept] for i in range(m)], np.uint64).reshape(m, 2)
 
     def validate_hits(self, reset: bool = False) -> np.ndarray:
         """sr_core_validate_hits: drains, then [lines, bytes] per reason (row 0: the OK lines)."""

@@ -28,6 +28,7 @@
 #include "regroup_kernel.hpp"
 #include "route_host.hpp"
 #include "rules_kernel.hpp"
+#include "sample_kernel.hpp"
 #include "stats_kernel.hpp"
 #include "validate_kernel.hpp"
 
@@ -103,6 +104,15 @@ struct sr_ctx {
     uint64_t *d_vhash;            // ... these hashes, when the coalescing follows ...
     size_t d_vhash_cap;
     uint64_t *d_vcounts;          // ... and these four counts
+    SampleStage sample;           // sr_sample_open: the sample-rate stage's table, hits and scratch
+    int sample_on;                // sr_set_sample: submissions thin hot names between the name rules and the coalescing
+    sr_record *d_sout;            // ... into these records (one per byte of the largest batch) ...
+    size_t d_sout_cap;
+    uint64_t *d_shash;            // ... these hashes, when the coalescing follows ...
+    size_t d_shash_cap;
+    uint64_t *d_scounts;          // ... and these four counts
+    uint64_t sample_subs;         // submissions accepted since sr_set_sample: the next one's seed_add
+    size_t d_in_cap;              // d_in's bytes once a switch has allocated it again (0: max_batch)
     // packing knobs (sr_set_knob): forced chunk lines (0: by shape), XCD-local chunks, chain walked in emit
     uint32_t mtu_chunk;
     int mtu_xcd, mtu_walk;
@@ -141,6 +151,11 @@ struct sr_ctx {
         // sr_set_validate: {4 counts, input records} (one more page-locked allocation)
         uint64_t *vhost, *vdev;
         int validated;            // the batch in the slot was submitted with the line grammar on
+        // sr_set_sample: rewritten text | {4 counts, input records} (one more page-locked allocation)
+        uint8_t *shost, *sdev;
+        size_t stext_cap;
+        int sampled;              // the batch in the slot was submitted with the sample rates on ...
+        uint64_t sseed;           // ... under this seed (the configuration's + seed_add)
         // sr_set_logtext: text | offsets | levels | {total, messages} | staged prefixes | staged ends
         uint8_t *lhost, *ldev;
         size_t ltext_cap, lmsg_cap;
@@ -283,6 +298,13 @@ void sr_close(sr_ctx *c) {
     free_ptr(c->validate.d_hits);
     free_ptr(c->validate.d_reason);
     free_ptr(c->validate.d_tiles);
+    free_ptr(c->sample.d_table);
+    free_ptr(c->sample.d_hits);
+    free_ptr(c->sample.d_scratch);
+    free_ptr(c->sample.d_tiles);
+    free_ptr(c->d_sout);
+    free_ptr(c->d_shash);
+    free_ptr(c->d_scounts);
     free_ptr(c->d_vout);
     free_ptr(c->d_vhash);
     free_ptr(c->d_vcounts);
@@ -294,6 +316,7 @@ void sr_close(sr_ctx *c) {
         if (sl.chost) (void)hipHostFree(sl.chost);
         if (sl.rhost) (void)hipHostFree(sl.rhost);
         if (sl.vhost) (void)hipHostFree(sl.vhost);
+        if (sl.shost) (void)hipHostFree(sl.shost);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1271,6 +1294,24 @@ int sr_coalesce_close(sr_ctx *c) {
     return 0;
 }
 
+// The input buffer of the host-memory path for the switches that allocate it again: the batch, then
+// SR_SAMPLE_APPEND_CAPACITY(max_batch) of room for the rewritten lines (sr_set_sample), then max_batch of room for the
+// merged text (sr_set_coalesce). Grown, never shrunk; every slot is idle.
+static int input_reserve(sr_ctx *c, bool sample, bool coalesce) {
+    const uint64_t full = c->ds.max_batch;
+    const uint64_t arena = sample ? (uint64_t)SR_SAMPLE_APPEND_CAPACITY(full) : 0u;
+    const uint64_t total = full + arena + (coalesce ? full : 0u);
+    if (total > 0xFFFFFFF0ull || (coalesce && full + arena > SR_COALESCE_MAX_BYTES)) return -EINVAL;
+    if (total <= (c->d_in_cap ? c->d_in_cap : full)) return 0;
+    (void)hipStreamSynchronize(c->stream);
+    uint8_t *in = nullptr;
+    if (hipMalloc(&in, total) != hipSuccess) return -ENOMEM;
+    free_ptr(c->d_in);
+    c->d_in = in;
+    c->d_in_cap = total;
+    return 0;
+}
+
 int sr_set_coalesce(sr_ctx *c, const sr_coalesce_config *cfg) {
     if (!c) return -EINVAL;
     for (int k = 0; k < 3; ++k)
@@ -1287,16 +1328,12 @@ int sr_set_coalesce(sr_ctx *c, const sr_coalesce_config *cfg) {
     }
     (void)hipSetDevice(c->device);
     if (!c->d_ccounts) {   // the first time: the input buffer again, with room for the merged text behind a batch
-        (void)hipStreamSynchronize(c->stream);
-        uint8_t *in = nullptr;
-        if (hipMalloc(&in, 2 * full) != hipSuccess) return -ENOMEM;
+        const int rc = input_reserve(c, c->d_scounts != nullptr, true);
+        if (rc) return rc;
         if (hipMalloc(&c->d_ccounts, 4 * sizeof(uint64_t)) != hipSuccess) {
             c->d_ccounts = nullptr;
-            free_ptr(in);
             return -ENOMEM;
         }
-        free_ptr(c->d_in);
-        c->d_in = in;
     }
     c->coalesce_on = 1;
     return 0;
@@ -1728,6 +1765,198 @@ int sr_route_pack_validate(sr_ctx *c, int slot, uint64_t counts[4]) {
     return 0;
 }
 
+// ---- sample rates (sample_kernel.hpp, sample_host.hpp) ------------------------------------------------------
+int sr_sample_open(sr_ctx *c, const sr_sample_config *cfg) {
+    if (!c) return -EINVAL;
+    SampleStage &st = c->sample;
+    if (st.open) return -EBUSY;
+    (void)hipSetDevice(c->device);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;   // it allocates: not inside a capture
+    if (hipStreamIsCapturing(c->stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return -EINVAL;
+    if (sample_check(cfg) != 0) return -EINVAL;
+    const uint32_t slots = sample_resolve_slots(cfg->slots);
+    int rc = 0;
+    if (hipMalloc(&st.d_table, (size_t)kSampleMaxBatches * slots * sizeof(uint32_t)) != hipSuccess) {
+        st.d_table = nullptr;
+        rc = -ENOMEM;
+    } else if (hipMalloc(&st.d_hits, kSampleHitCells * sizeof(unsigned long long)) != hipSuccess) {
+        st.d_hits = nullptr;
+        rc = -ENOMEM;
+    } else if (hipMemsetAsync(st.d_hits, 0, kSampleHitCells * sizeof(unsigned long long), c->stream) != hipSuccess) {
+        rc = -EIO;
+    }
+    if (rc) {
+        (void)hipGetLastError();
+        free_ptr(st.d_table);
+        free_ptr(st.d_hits);
+        memset(&st, 0, sizeof(st));
+        return rc;
+    }
+    st.cfg = *cfg;
+    st.slots = slots;
+    st.open = 1;
+    return 0;
+}
+
+int sr_sample_close(sr_ctx *c) {
+    if (!c) return -EINVAL;
+    SampleStage &st = c->sample;
+    for (int k = 0; k < 3; ++k)
+        if (c->slot[k].busy) return -EBUSY;
+    if (!st.open) return 0;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    free_ptr(st.d_table);
+    free_ptr(st.d_hits);
+    free_ptr(st.d_scratch);
+    free_ptr(st.d_tiles);
+    memset(&st, 0, sizeof(st));
+    c->sample_on = 0;
+    return 0;
+}
+
+int sr_sample(sr_ctx *c, const sr_sample_batch *batches, size_t count) {
+    static_assert(kSampleMaxBatches == (int)SR_MAX_BATCHES_PER_LAUNCH, "launch batch limit");
+    if (!c || !c->sample.open || !batches || count == 0 || count > (size_t)kSampleMaxBatches) return -EINVAL;
+    SampleStage &st = c->sample;
+    size_t records = 0, tiles = 0;   // the scratch's sizes, by max_records
+    uint64_t grid_tiles = 0;         // the grid's bound only (the kernels number the tiles by the device's counts)
+    for (size_t j = 0; j < count; ++j) {
+        const sr_sample_batch &b = batches[j];
+        if (!b.d_n_records || !b.d_counts || !b.d_hashes || ((b.nbytes || b.append_cap) && !b.d_bytes)) return -EINVAL;
+        if (b.max_records && (!b.d_recs || !b.d_out || b.d_out == b.d_recs)) return -EINVAL;
+        if (b.d_hashes_out == b.d_hashes) return -EINVAL;
+        if ((const void *)b.d_counts == (const void *)b.d_n_records) return -EINVAL;   // read after the counts are written
+        if (b.nbytes > SR_SAMPLE_MAX_BYTES || b.max_records > 0xFFFFFFF0ull) return -EINVAL;
+        if (b.append_cap > 0xFFFFFFF0ull || (uint64_t)b.nbytes + b.append_cap > 0xFFFFFFF0ull) return -EINVAL;
+        records += b.max_records;
+        tiles += (b.max_records + kSampleTile - 1) / kSampleTile;
+        const uint64_t likely = (uint64_t)b.nbytes / kSampleGridLineBytes + 1u;
+        const uint64_t room = b.max_records < likely ? b.max_records : likely;
+        grid_tiles += (room + kSampleTile - 1) / kSampleTile;
+    }
+    (void)hipSetDevice(c->device);
+    int rc;
+    if ((rc = grow((void **)&st.d_scratch, &st.scratch_cap, records, sizeof(uint32_t)))) return rc;
+    if ((rc = grow((void **)&st.d_tiles, &st.tiles_cap, tiles, sizeof(uint4)))) return rc;
+    SampleArgs a;
+    memset(&a, 0, sizeof(a));
+    size_t at = 0;
+    for (size_t j = 0; j < count; ++j) {
+        const sr_sample_batch &b = batches[j];
+        SampleBatchArg &o = a.b[j];
+        o.bytes = b.d_bytes;
+        o.recs = b.d_recs;
+        o.n_records = b.d_n_records;
+        o.hashes = b.d_hashes;
+        o.out = b.d_out;
+        o.hashes_out = b.d_hashes_out;
+        o.step = b.d_step;
+        o.counts = b.d_counts;
+        o.scratch = st.d_scratch + at;
+        o.table = st.d_table + j * (size_t)st.slots;   // back to back: sample_clear_kernel zeroes them as one
+        o.append_cap = b.append_cap;
+        o.seed = st.cfg.seed + b.seed_add;
+        o.nbytes = (uint32_t)b.nbytes;
+        o.max_records = (uint32_t)b.max_records;
+        at += b.max_records;
+    }
+    a.hits = st.d_hits;
+    a.tiles = st.d_tiles;
+    a.nb = (uint32_t)count;
+    a.nds = c->ds.nds;
+    a.slots = st.slots;
+    a.limit = st.cfg.limit;
+    a.types = st.cfg.types;
+    if (grid_tiles) {
+        const dim3 grid((uint32_t)(grid_tiles < (uint64_t)kSampleGroups ? grid_tiles : (uint64_t)kSampleGroups));
+        const uint64_t clear = ((uint64_t)count * st.slots / 4u + kSampleBlock - 1) / kSampleBlock;
+        hipLaunchKernelGGL(sample_clear_kernel, dim3((uint32_t)(clear < (uint64_t)kSampleGroups ? clear : (uint64_t)kSampleGroups)),
+                           dim3(kSampleBlock), 0, c->stream, a);
+        hipLaunchKernelGGL(sample_count_kernel, grid, dim3(kSampleBlock), 0, c->stream, a);
+        hipLaunchKernelGGL(sample_sum_kernel, grid, dim3(kSampleBlock), 0, c->stream, a);
+        hipLaunchKernelGGL(sample_scan_kernel, dim3((uint32_t)count), dim3(kSampleScanBlock), 0, c->stream, a);
+        hipLaunchKernelGGL(sample_emit_kernel, grid, dim3(kSampleBlock), 0, c->stream, a);
+    } else {   // no batch has room for a record: the counts alone
+        hipLaunchKernelGGL(sample_scan_kernel, dim3((uint32_t)count), dim3(kSampleScanBlock), 0, c->stream, a);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
+
+int sr_sample_read(sr_ctx *c, sr_sample_hits *hits, size_t n) {
+    static_assert(sizeof(sr_sample_hits) == 2 * sizeof(unsigned long long), "a hit is two cells");
+    if (!c || !c->sample.open || (n && !hits)) return -EINVAL;
+    const size_t m = n < (size_t)SR_SAMPLE_STEPS ? n : (size_t)SR_SAMPLE_STEPS;
+    (void)hipSetDevice(c->device);
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return -EIO;
+    if (m && hipMemcpy(hits, c->sample.d_hits, m * sizeof(sr_sample_hits), hipMemcpyDeviceToHost) != hipSuccess) return -EIO;
+    return (int)m;
+}
+
+int sr_sample_reset(sr_ctx *c) {
+    if (!c || !c->sample.open) return -EINVAL;
+    (void)hipSetDevice(c->device);
+    return hipMemsetAsync(c->sample.d_hits, 0, kSampleHitCells * sizeof(unsigned long long), c->stream) == hipSuccess ? 0 : -EIO;
+}
+
+int sr_sample_check(const sr_sample_config *cfg) { return sample_check(cfg); }
+
+int sr_sample_parse(const uint8_t *line, size_t len, uint32_t types, uint32_t *ins, uint32_t *type_bit) {
+    if (!line) return -EINVAL;
+    return sample_parse(line, len, types, ins, type_bit);
+}
+
+uint32_t sr_sample_step(uint32_t limit, uint64_t count) { return sample_step(limit, count); }
+
+int sr_sample_keep(uint64_t hash, uint64_t seed, uint64_t index, uint32_t step) {
+    if (step >= SR_SAMPLE_STEPS) return -EINVAL;
+    return (int)sample_keep(hash, seed, index, step);
+}
+
+const char *sr_sample_rate_text(uint32_t step) { return sample_rate_text(step); }
+
+size_t sr_sample_rewrite(uint8_t *dst, const uint8_t *line, size_t len, uint32_t ins, uint32_t step) {
+    return sample_rewrite(dst, line, len, ins, step);
+}
+
+int sr_sample_parse_spec(const char *text, sr_sample_config *cfg_out) { return sample_parse_spec(text, cfg_out); }
+
+int sr_set_sample(sr_ctx *c, const sr_sample_config *cfg) {
+    if (!c) return -EINVAL;
+    for (int k = 0; k < 3; ++k)
+        if (c->slot[k].busy) return -EBUSY;
+    if (!cfg) {
+        c->sample_on = 0;
+        return 0;
+    }
+    int rc = sample_check(cfg);   // a bad configuration leaves the stage as it was
+    if (rc) return rc;
+    if (c->ds.max_batch > SR_SAMPLE_MAX_BYTES) return -EINVAL;
+    (void)hipSetDevice(c->device);
+    if ((rc = input_reserve(c, true, c->d_ccounts != nullptr))) return rc;
+    if (c->sample.open && (rc = sr_sample_close(c))) return rc;
+    if ((rc = sr_sample_open(c, cfg))) return rc;
+    if (!c->d_scounts && hipMalloc(&c->d_scounts, 4 * sizeof(uint64_t)) != hipSuccess) {
+        c->d_scounts = nullptr;
+        return -ENOMEM;
+    }
+    c->sample_subs = 0;
+    c->sample_on = 1;
+    return 0;
+}
+
+int sr_route_pack_sample(sr_ctx *c, int slot, const uint8_t **text, size_t *len, uint64_t counts[4], uint64_t *seed) {
+    if (!c || !text || !len || !counts || !seed || slot < 0 || slot > 2) return -EINVAL;
+    const sr_ctx::Slot &sl = c->slot[slot];
+    if (sl.busy || !sl.sampled || !sl.shost) return -EBUSY;
+    const uint64_t *hc = (const uint64_t *)(sl.shost + ((sl.stext_cap + 255) & ~(size_t)255));
+    for (int q = 0; q < 4; ++q) counts[q] = hc[q];
+    *text = sl.shost;
+    *len = (size_t)(hc[3] < sl.stext_cap ? hc[3] : sl.stext_cap);
+    *seed = sl.sseed;
+    return hc[3] > sl.stext_cap ? -ENOSPC : 0;
+}
+
 // Host outputs of a slot for batches of up to nbytes (grown, never shrunk; the slot is idle).
 static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static int slot_reserve(sr_ctx *c, int k, size_t nbytes) {
@@ -1860,6 +2089,25 @@ static int slot_validate_reserve(sr_ctx *c, int k) {
     return 0;
 }
 
+// sr_set_sample: the slot's rewritten text and counts (grown, never shrunk; the slot is idle): text | 5 u64
+static int slot_sample_reserve(sr_ctx *c, int k, size_t text_bytes) {
+    sr_ctx::Slot &sl = c->slot[k];
+    if (sl.shost && text_bytes <= sl.stext_cap) return 0;
+    if (sl.shost) (void)hipHostFree(sl.shost);
+    sl.shost = sl.sdev = nullptr;
+    sl.stext_cap = 0;
+    void *h = nullptr, *d = nullptr;
+    if (hipHostMalloc(&h, up256(text_bytes) + 256, hipHostMallocMapped) != hipSuccess) return -ENOMEM;
+    if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
+        (void)hipHostFree(h);
+        return -EIO;
+    }
+    sl.shost = (uint8_t *)h;
+    sl.sdev = (uint8_t *)d;
+    sl.stext_cap = text_bytes;
+    return 0;
+}
+
 // sr_set_logtext: the slot's text arena, index, totals and the staging of prefixes and ends (sized by the
 // switch, which only changes while every slot is idle)
 struct LogLayout {
@@ -1923,10 +2171,15 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
     // every buffer is sized for the context's largest batch at the first submission (an empty one
     // pre-allocates): growing page-locked memory or freeing device memory mid-stream would stall the
     // data thread while its socket fills
-    const size_t full = c->ds.max_batch, fullp = (size_t)SR_MAX_PACKETS(full, nds);
-    if ((rc = slot_reserve(c, k, full))) return rc;
+    // (with the sample rates on a kept line may be up to 8 bytes longer: the thinned batch has at most
+    // SR_SAMPLE_APPEND_CAPACITY(nbytes) bytes, which then sizes the packets and the payloads)
+    const bool sample = c->sample_on != 0;
+    const size_t full = c->ds.max_batch, fulls = sample ? (size_t)SR_SAMPLE_APPEND_CAPACITY(full) : full;
+    const size_t fullp = (size_t)SR_MAX_PACKETS(fulls, nds);
+    if ((rc = slot_reserve(c, k, fulls))) return rc;
     if (c->trace && (rc = slot_trace_reserve(c, k, full))) return rc;
-    if (c->payloads && (rc = slot_payload_reserve(c, k, full))) return rc;
+    if (c->payloads && (rc = slot_payload_reserve(c, k, fulls))) return rc;
+    if (sample && (rc = slot_sample_reserve(c, k, (size_t)SR_SAMPLE_APPEND_CAPACITY(full)))) return rc;
     if (c->logtext && (rc = slot_log_reserve(c, k))) return rc;
     const bool coalesce = c->coalesce_on != 0;
     if (coalesce && (rc = slot_coalesce_reserve(c, k, full))) return rc;
@@ -1940,7 +2193,9 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
         return -ENOMEM;
     }
     const size_t cap = nbytes ? nbytes : 1;   // never more lines than bytes
-    const size_t pcap = (size_t)SR_MAX_PACKETS(cap, nds);
+    const size_t arena = sample ? (size_t)SR_SAMPLE_APPEND_CAPACITY(nbytes) : 0;   // behind the batch in d_in
+    const size_t pcap = (size_t)SR_MAX_PACKETS(sample ? (size_t)SR_SAMPLE_APPEND_CAPACITY(cap) : cap, nds);
+    const uint64_t seed_add = c->sample_subs;
     if ((rc = grow((void **)&c->d_out, &c->d_out_cap, full, sizeof(sr_record)))) return rc;
     if ((rc = grow((void **)&c->d_sorted, &c->d_sorted_cap, full, sizeof(sr_record)))) return rc;
     if ((rc = grow((void **)&c->d_packets, &c->d_packets_cap, fullp, sizeof(sr_packet)))) return rc;
@@ -1979,13 +2234,15 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
         // up to 1024 the probes note the dead shards themselves
         // TRACE (sr_set_trace) needs every line's hash too (sr-main.c:91), and so do the name statistics
         uint64_t *hashes = nullptr;
-        if (c->trace || log_trace || c->name_stats || coalesce || c->ds.replay_wants_hashes()) {
+        if (c->trace || log_trace || c->name_stats || coalesce || sample || c->ds.replay_wants_hashes()) {
             if ((rc = grow((void **)&c->d_hash, &c->d_hash_cap, full, sizeof(uint64_t)))) return rc;
             hashes = c->d_hash;
         }
         const sr_batch rb{c->d_in, nbytes, c->d_out, cap, hashes, c->d_count, c->d_probed};
-        if (rules || validate) {   // route, validate, rules, coalesce, pack: each stage that is on reads the one
-                                   // before's records, count and (for the coalescing) hashes
+        if (rules || validate || sample) {   // route, validate, rules, sample, coalesce, pack: each stage that is on
+                                             // reads the one before's records, count and (for the sample rates and
+                                             // the coalescing) hashes
+            const bool later_hs = coalesce || sample;   // a later stage takes the hashes
             if (coalesce && !c->d_cout && hipMalloc(&c->d_cout, full * sizeof(sr_record)) != hipSuccess) {
                 c->d_cout = nullptr;
                 return -ENOMEM;
@@ -1995,29 +2252,39 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
                                    rb.d_probed_dead);
             if ((rc = launch_variant(c->ds, p, c->stream))) return rc;
             const sr_record *recs = c->d_out;
-            const uint64_t *cnt = c->d_count, *hs = coalesce ? c->d_hash : nullptr;
+            const uint64_t *cnt = c->d_count, *hs = later_hs ? c->d_hash : nullptr;
             if (validate) {
                 if ((rc = grow((void **)&c->d_vout, &c->d_vout_cap, full, sizeof(sr_record)))) return rc;
-                if (coalesce && (rc = grow((void **)&c->d_vhash, &c->d_vhash_cap, full, sizeof(uint64_t)))) return rc;
-                const sr_validate_batch vb{c->d_in, nbytes, recs, cnt, cap, c->d_vout, hs, coalesce ? c->d_vhash : nullptr,
+                if (later_hs && (rc = grow((void **)&c->d_vhash, &c->d_vhash_cap, full, sizeof(uint64_t)))) return rc;
+                const sr_validate_batch vb{c->d_in, nbytes, recs, cnt, cap, c->d_vout, hs, later_hs ? c->d_vhash : nullptr,
                                            nullptr, c->d_vcounts};
                 if ((rc = sr_validate(c, &vb, 1))) return rc;
                 recs = c->d_vout;
                 cnt = c->d_vcounts;
-                hs = coalesce ? c->d_vhash : nullptr;
+                hs = later_hs ? c->d_vhash : nullptr;
             }
             if (rules) {
                 if ((rc = grow((void **)&c->d_rout, &c->d_rout_cap, full, sizeof(sr_record)))) return rc;
-                if (coalesce && (rc = grow((void **)&c->d_rhash, &c->d_rhash_cap, full, sizeof(uint64_t)))) return rc;
-                const sr_rules_batch ub{c->d_in, nbytes, recs, cnt, cap, c->d_rout, hs, coalesce ? c->d_rhash : nullptr,
+                if (later_hs && (rc = grow((void **)&c->d_rhash, &c->d_rhash_cap, full, sizeof(uint64_t)))) return rc;
+                const sr_rules_batch ub{c->d_in, nbytes, recs, cnt, cap, c->d_rout, hs, later_hs ? c->d_rhash : nullptr,
                                         nullptr, c->d_rcounts};
                 if ((rc = sr_rules(c, &ub, 1))) return rc;
                 recs = c->d_rout;
                 cnt = c->d_rcounts;
-                hs = coalesce ? c->d_rhash : nullptr;
+                hs = later_hs ? c->d_rhash : nullptr;
+            }
+            if (sample) {   // the rewritten lines go behind the batch; the coalescing takes both as its batch
+                if ((rc = grow((void **)&c->d_sout, &c->d_sout_cap, full, sizeof(sr_record)))) return rc;
+                if (coalesce && (rc = grow((void **)&c->d_shash, &c->d_shash_cap, full, sizeof(uint64_t)))) return rc;
+                const sr_sample_batch mb{c->d_in, nbytes, arena, recs, cnt, cap, hs, c->d_sout, coalesce ? c->d_shash : nullptr,
+                                         nullptr, c->d_scounts, seed_add};
+                if ((rc = sr_sample(c, &mb, 1))) return rc;
+                recs = c->d_sout;
+                cnt = c->d_scounts;
+                hs = coalesce ? c->d_shash : nullptr;
             }
             if (coalesce) {
-                const sr_coalesce_batch cb{c->d_in, nbytes, nbytes, recs, cnt, cap, hs, c->d_cout, c->d_ccounts};
+                const sr_coalesce_batch cb{c->d_in, nbytes + arena, nbytes, recs, cnt, cap, hs, c->d_cout, c->d_ccounts};
                 if ((rc = sr_coalesce(c, &cb, 1))) return rc;
                 recs = c->d_cout;
                 cnt = c->d_ccounts;
@@ -2067,8 +2334,9 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
     // by the input's count
     // (with the name rules on rules_out_kernel does, unless the coalescing is on too)
     // (and with the line grammar on validate_out_kernel does, unless one of those two is on too)
-    o.recs = (c->trace && nbytes && !coalesce && !rules && !validate) ? c->d_out : nullptr;
-    o.hashes = (c->trace && nbytes && !coalesce && !rules && !validate) ? c->d_hash : nullptr;
+    // (and with the sample rates on sample_out_kernel does, unless one of those three is on too)
+    o.recs = (c->trace && nbytes && !coalesce && !rules && !validate && !sample) ? c->d_out : nullptr;
+    o.hashes = (c->trace && nbytes && !coalesce && !rules && !validate && !sample) ? c->d_hash : nullptr;
     o.h_recs = c->trace ? (sr_record *)sl.tdev : nullptr;
     o.h_hashes = c->trace ? (uint64_t *)(sl.tdev + up256(sl.trec_cap * sizeof(sr_record))) : nullptr;
     // one workgroup per 512 records (two per thread), at most 1024 workgroups (grid-stride beyond)
@@ -2083,7 +2351,7 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
             for (int q = 0; q < 5; ++q) hc[q] = 0;   // the slot is idle: nothing is in flight that writes here
         } else {
             CoalesceOut co;
-            co.text = c->d_in + nbytes;
+            co.text = c->d_in + nbytes + arena;
             co.counts = c->d_ccounts;
             co.n_records = c->d_count;
             co.text_cap = nbytes < sl.ctext_cap ? nbytes : sl.ctext_cap;
@@ -2139,10 +2407,35 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
             if (hipGetLastError() != hipSuccess) return -EIO;
         }
     }
+    sl.sampled = sample;
+    if (sample) {   // the rewritten text, the counts and the input's record count into the slot's page-locked memory
+        uint64_t *const hc = (uint64_t *)(sl.shost + up256(sl.stext_cap));
+        sl.sseed = c->sample.cfg.seed + seed_add;
+        if (nbytes == 0) {
+            for (int q = 0; q < 5; ++q) hc[q] = 0;   // the slot is idle: nothing is in flight that writes here
+        } else {
+            const bool tr = c->trace && !coalesce && !rules && !validate;
+            SampleOut so;
+            so.text = c->d_in + nbytes;
+            so.counts = c->d_scounts;
+            so.n_records = c->d_count;
+            so.text_cap = arena < sl.stext_cap ? arena : sl.stext_cap;
+            so.rec_cap = tr ? sl.trec_cap : 0;
+            so.h_text = sl.sdev;
+            so.h_counts = (uint64_t *)(sl.sdev + up256(sl.stext_cap));
+            so.recs = tr ? c->d_out : nullptr;
+            so.hashes = tr ? c->d_hash : nullptr;
+            so.h_recs = tr ? (sr_record *)sl.tdev : nullptr;
+            so.h_hashes = tr ? (uint64_t *)(sl.tdev + up256(sl.trec_cap * sizeof(sr_record))) : nullptr;
+            hipLaunchKernelGGL(sample_out_kernel, dim3((uint32_t)(want < 1024 ? (want ? want : 1) : 1024)),
+                               dim3(kSampleBlock), 0, c->stream, so);
+            if (hipGetLastError() != hipSuccess) return -EIO;
+        }
+    }
     sl.payloaded = c->payloads;
     if (c->payloads) {   // the packets' bytes straight into the slot's page-locked memory; the host holds the carries
         const size_t o_off = up256(sl.pay_cap), o_tot = o_off + up256((sl.poff_cap + 1) * sizeof(uint32_t));
-        const sr_payload_batch yb{c->d_in, coalesce ? 2 * nbytes : nbytes, c->d_sorted, nbytes ? cap : 0, c->d_packets, pcap < sl.poff_cap ? pcap : sl.poff_cap,
+        const sr_payload_batch yb{c->d_in, nbytes + arena + (coalesce ? nbytes : 0), c->d_sorted, nbytes ? cap : 0, c->d_packets, pcap < sl.poff_cap ? pcap : sl.poff_cap,
                                   c->d_mcounts, f_out, nullptr, nullptr, sl.pdev, sl.pay_cap,
                                   (uint32_t *)(sl.pdev + o_off), (uint64_t *)(sl.pdev + o_tot)};
         if ((rc = payloads_impl(c, &yb, 1))) return rc;
@@ -2176,6 +2469,7 @@ static int pack_submit(sr_ctx *c, int k, const uint8_t *bytes, size_t nbytes, co
     }
     if (hipEventRecord(sl.done, c->stream) != hipSuccess) return -EIO;
     sl.busy = 1;
+    if (sample) ++c->sample_subs;
     return 0;
 }
 
@@ -2207,6 +2501,7 @@ int sr_route_pack_trace(sr_ctx *c, int slot, const sr_record **records, const ui
     const uint64_t nr = (sl.coalesced && sl.chost) ? ((const uint64_t *)(sl.chost + up256(sl.ctext_cap)))[4]
                         : (sl.ruled && sl.rhost)   ? sl.rhost[4]
                         : (sl.validated && sl.vhost) ? sl.vhost[4]
+                        : (sl.sampled && sl.shost) ? ((const uint64_t *)(sl.shost + up256(sl.stext_cap)))[4]
                                                    : sl.counts[2];
     *n = (size_t)(nr < sl.trec_cap ? nr : sl.trec_cap);
     *records = (const sr_record *)sl.thost;
